@@ -10,7 +10,11 @@ IHAVE emission, mcache shift).  `--workload config3` runs BASELINE configs[2]
 (1M peers, 1 topic) instead.
 
 Contract: python bench.py --gpus N --steps K --warmup W; with N > 1 it is
-launched by torch.distributed.run, one rank per GPU.  By default the ranks
+launched by torch.distributed.run, one rank per GPU.  Such a plain run sets up,
+warms up, times the K steps and prints the result line; `--full` adds what
+takes work of its own (the rooflines' byte models, the device memory held, the
+CPU baseline), and `--dump-outputs DIR` writes what the last timed step left
+(dump_outputs below).  By default the ranks
 PARTITION the one 1M-peer graph: rank r simulates a contiguous
 node range and exchanges its nodes' RPCs with the other ranks once per hop over
 RCCL (all-gather of frontier lists / IWANT arena / IHAVE rows, all-to-all-v of
@@ -30,7 +34,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(REPO, "go-libp2p-pubsub_amd"))
 
 from pubsub_amd import (GS_BEHAVE_GRAFT_SPAM, GS_BEHAVE_IHAVE_SPAM, GS_BEHAVE_IWANT_SPAM,  # noqa: E402
-                        GS_MSG_PHANTOM, GS_MSG_REJECT, DefaultPeerGaterParams, Millisecond, NewGossipSub,
+                        GS_MSG_PHANTOM, GS_MSG_REJECT, GS_ROUTER_GOSSIPSUB, DefaultPeerGaterParams, Millisecond, NewGossipSub,
                         WithBehaviour, WithDevice, WithHop, WithMessageWindow, WithPartition, WithPeerGater,
                         WithPeerScore, WithSeed, WithValidation, eth2_peer_score_params, eth2_thresholds)
 from pubsub_amd import graphs  # noqa: E402
@@ -345,13 +349,132 @@ def cpu_baseline_config2(wl, lib, threads, seconds, scale=1):
                       f"({hps} hops), {dt:.1f} s"}
 
 
+def dump_outputs(eng, out_dir, counters, rank=0):
+    """--dump-outputs: what a caller of the timed path reads back after its
+    last step, as out_dir/<name>.npy (float64; under 64 MB in all): the event
+    counters and, of a scored gossipsub engine, the peer scores, behaviour
+    penalties, mesh memberships and per-topic score counters of fixed seeded
+    samples of this rank's edges (ranks above 0 write to out_dir/rank<r>/).
+    Graph, schedule and samples are seeded, so equal arguments give equal files."""
+    if rank:
+        out_dir = os.path.join(out_dir, f"rank{rank}")
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    save("counters", [counters[k] for k in sorted(counters)])  # cumulative, keys in sorted order
+    if eng.router != GS_ROUTER_GOSSIPSUB or eng.score_params is None:  # floodsub / randomsub: no more state
+        return
+    e0, e1 = eng.edge_range
+    rng = np.random.default_rng(20240611)
+    wide = np.unique(rng.integers(e0, e1, min(e1 - e0, 1 << 20)))          # <= 8 MB per array
+    narrow = np.unique(rng.integers(e0, e1, min(e1 - e0, (1 << 18) // eng.T)))  # x T topics: <= 2 MB per array
+    save("sample_edges", wide)
+    save("sample_edges_topics", narrow)
+    save("scores", eng.scores()[wide])
+    save("behaviour_penalty", eng.behaviour_penalty()[wide])
+    mesh = eng.mesh()  # a topic bit mask per edge
+    save("mesh_count", np.bitwise_count(mesh[wide]))
+    save("mesh_topics", (mesh[narrow][:, None] >> np.arange(eng.T, dtype=np.uint64)) & np.uint64(1))
+    st = eng.topic_stats_at(narrow)
+    for k in ("fmd", "mmd", "mfp", "imd", "mesh_time"):
+        save("topic_" + k, st[k])
+
+
+def roofline_report(args, eng, wl, kstats, events, c0, c1, hop0, prop_hops, partitioned):
+    """--full: (roofline of the heaviest kernel with a byte model, the other
+    kernels' rooflines) over the timed window, from the engine's HIP-event
+    kernel times and algorithmic_bytes."""
+    hps = hops_per_step(wl)
+    gossip = wl.get("router", "gossipsub") == "gossipsub"
+    nh = args.steps * hps
+    per_hop = {"events_per_round": {k: v / args.steps for k, v in events.items()},
+               "deliveries": (c1["deliveries"] - c0["deliveries"]) / nh,
+               "published": (c1["published"] - c0["published"]) / nh,
+               "transmissions": (c1["transmissions"] - c0["transmissions"]) / nh,
+               "iwant_served": (c1["iwant_served"] - c0["iwant_served"]) / nh,
+               "active_words": float(np.mean([active_words(eng, wl, hop0 + i) for i in range(nh)])) if gossip
+               else wl["topics"] * wl["slots"] / 64.0,
+               "prop_hops_per_step": prop_hops, "steps": args.steps,
+               "mesh_pairs": int(np.bitwise_count(eng.mesh()[eng.edge_range[0]:eng.edge_range[1]]).sum(dtype=np.int64))}
+    # the roofline is the heaviest kernel with an algorithmic byte model (phase
+    # B's control work has none: config3's steady state and config5 can be
+    # dominated by it, named in "dominant_kernel")
+    top = max(kstats, key=lambda k: kstats[k][0])
+    dom, bytes_per_launch, bytes_info = top, None, {}
+    for k in sorted(kstats, key=lambda k: -kstats[k][0]):
+        if not kstats[k][1]:
+            continue
+        b_k, info_k = algorithmic_bytes(k, eng, wl, per_hop)
+        if b_k:
+            dom, bytes_per_launch, bytes_info = k, b_k, info_k
+            break
+    total_ms, launches = kstats[dom]
+    avg_ms = total_ms / max(1, launches)
+    roofline = None
+    pmc = os.path.join(REPO, "profiles", f"pmc_traffic_{args.workload}.json")
+    pmc_recs = json.load(open(pmc)) if os.path.exists(pmc) and not partitioned else {}
+
+    def pmc_traffic(kernel):
+        # rocprofv3 PMC passes of this workload (scripts/gpu_pmc.sh + pmc_summary.py):
+        # FETCH_SIZE x 2 (gfx950's wide reads count half) + WRITE_SIZE,
+        # per launch; kernel names carry template arguments ("void k_phase_a<4, true>")
+        base = {"refresh": "k_refresh_rows"}.get(kernel, f"k_{kernel}")
+        # several instantiations (config3 / config5: the narrow counters of the
+        # first hops, then the wide ones): the one dispatched last is the
+        # timed window's
+        best = None
+        for name, rec in pmc_recs.items():
+            if name == base or name.startswith(f"void {base}<"):
+                if best is None or rec.get("last_dispatch", 0) > best.get("last_dispatch", 0):
+                    best = rec
+        return (best["traffic_bytes_est"], os.path.relpath(pmc, REPO)) if best else (None, None)
+
+    traffic, traffic_src = pmc_traffic(dom)
+    if bytes_per_launch and avg_ms > 0:
+        achieved = bytes_per_launch / (avg_ms / 1e3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    # the same launch priced at its measured DRAM bytes (PMC `traffic`, a
+                    # profile of this workload) instead of the algorithmic model: `frac`
+                    # uses the model named in `model`, this one what the HBM really moved
+                    "frac_traffic": (round(traffic / (avg_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
+                                     if traffic else None),
+                    "kernel": dom, "dominant_kernel": top,
+                    "avg_launch_ms": round(avg_ms, 4), "bytes_per_launch": int(bytes_per_launch),
+                    **{k: v for k, v in bytes_info.items()}}
+    # the score kernels' rooflines too (north-star target: >= 50% of HBM on
+    # score / propagation): refreshScores streams every (edge, topic) record
+    rooflines = {}
+    for k in ("refresh", "heartbeat", "phase_b", "phase_a"):
+        if k == dom:
+            continue
+        if k in kstats and kstats[k][1]:
+            b_k, _ = algorithmic_bytes(k, eng, wl, per_hop)
+            ms_k = kstats[k][0] / kstats[k][1]
+            ach = b_k / (ms_k / 1e3) / 1e9
+            rooflines[k] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(ach / HBM_PEAK_GBS, 4), "avg_launch_ms": round(ms_k, 4),
+                            "bytes_per_launch": int(b_k)}
+            rooflines[k]["traffic"], rooflines[k]["traffic_source"] = pmc_traffic(k)
+            if rooflines[k]["traffic"]:
+                rooflines[k]["frac_traffic"] = round(rooflines[k]["traffic"] / (ms_k / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
+    return roofline, rooflines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="config4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the rooflines (algorithmic byte models, PMC traffic), the device memory "
+                         "the engine holds and the CPU baseline (the oracle on a sample of the workload)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the engine's state as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--mode", default="partition", choices=["partition", "replicas"])
     ap.add_argument("--peers", type=int, default=0, help="override the workload's peer count (rehearsals)")
     ap.add_argument("--slots", type=int, default=0,
@@ -427,6 +550,8 @@ def main():
         from pubsub_amd import WithFrontierBitmaps, WithFrontierLists
         extra = tuple(extra) + ((WithFrontierLists if args.frontier == "lists" else WithFrontierBitmaps)(),)
     def dev_free():
+        if not args.full:
+            return None
         try:
             import torch
             return torch.cuda.mem_get_info(local)[0]
@@ -488,82 +613,12 @@ def main():
         events = dict(zip(ev_keys, (int(x) for x in dv.tolist())))
     deliveries = events["deliveries"]
     msgs_round = wl.get("msgs", MSGS_PER_ROUND)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, c1, rank)
     if rank != 0:
         dist.destroy_process_group()
         return
 
-    nh = args.steps * hps
-    per_hop = {"events_per_round": {k: v / args.steps for k, v in events.items()},
-               "deliveries": (c1["deliveries"] - c0["deliveries"]) / nh,
-               "published": (c1["published"] - c0["published"]) / nh,
-               "transmissions": (c1["transmissions"] - c0["transmissions"]) / nh,
-               "iwant_served": (c1["iwant_served"] - c0["iwant_served"]) / nh,
-               "active_words": float(np.mean([active_words(eng, wl, hop0 + i) for i in range(nh)])) if gossip
-               else wl["topics"] * wl["slots"] / 64.0,
-               "prop_hops_per_step": prop_hops, "steps": args.steps,
-               "mesh_pairs": int(np.bitwise_count(eng.mesh()[eng.edge_range[0]:eng.edge_range[1]]).sum(dtype=np.int64))}
-    # the roofline is the heaviest kernel with an algorithmic byte model (phase
-    # B's control work has none: config3's steady state and config5 can be
-    # dominated by it, named in "dominant_kernel")
-    top = max(kstats, key=lambda k: kstats[k][0])
-    dom, bytes_per_launch, bytes_info = top, None, {}
-    for k in sorted(kstats, key=lambda k: -kstats[k][0]):
-        if not kstats[k][1]:
-            continue
-        b_k, info_k = algorithmic_bytes(k, eng, wl, per_hop)
-        if b_k:
-            dom, bytes_per_launch, bytes_info = k, b_k, info_k
-            break
-    total_ms, launches = kstats[dom]
-    avg_ms = total_ms / max(1, launches)
-    roofline = None
-    pmc = os.path.join(REPO, "profiles", f"pmc_traffic_{args.workload}.json")
-    pmc_recs = json.load(open(pmc)) if os.path.exists(pmc) and not partitioned else {}
-
-    def pmc_traffic(kernel):
-        # rocprofv3 PMC passes of this workload (scripts/gpu_pmc.sh + pmc_summary.py):
-        # FETCH_SIZE x 2 (gfx950 wide-read correction, MI355X_MICROARCH.md) + WRITE_SIZE,
-        # per launch; kernel names carry template arguments ("void k_phase_a<4, true>")
-        base = {"refresh": "k_refresh_rows"}.get(kernel, f"k_{kernel}")
-        # several instantiations (config3 / config5: the narrow counters of the
-        # first hops, then the wide ones): the one dispatched last is the
-        # timed window's
-        best = None
-        for name, rec in pmc_recs.items():
-            if name == base or name.startswith(f"void {base}<"):
-                if best is None or rec.get("last_dispatch", 0) > best.get("last_dispatch", 0):
-                    best = rec
-        return (best["traffic_bytes_est"], os.path.relpath(pmc, REPO)) if best else (None, None)
-
-    traffic, traffic_src = pmc_traffic(dom)
-    if bytes_per_launch and avg_ms > 0:
-        achieved = bytes_per_launch / (avg_ms / 1e3) / 1e9
-        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                    # the same launch priced at its measured DRAM bytes (PMC `traffic`, a
-                    # profile of this workload) instead of the algorithmic model: `frac`
-                    # uses the model named in `model`, this one what the HBM really moved
-                    "frac_traffic": (round(traffic / (avg_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
-                                     if traffic else None),
-                    "kernel": dom, "dominant_kernel": top,
-                    "avg_launch_ms": round(avg_ms, 4), "bytes_per_launch": int(bytes_per_launch),
-                    **{k: v for k, v in bytes_info.items()}}
-    # the score kernels' rooflines too (north-star target: >= 50% of HBM on
-    # score / propagation): refreshScores streams every (edge, topic) record
-    rooflines = {}
-    for k in ("refresh", "heartbeat", "phase_b", "phase_a"):
-        if k == dom:
-            continue
-        if k in kstats and kstats[k][1]:
-            b_k, _ = algorithmic_bytes(k, eng, wl, per_hop)
-            ms_k = kstats[k][0] / kstats[k][1]
-            ach = b_k / (ms_k / 1e3) / 1e9
-            rooflines[k] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": round(ach / HBM_PEAK_GBS, 4), "avg_launch_ms": round(ms_k, 4),
-                            "bytes_per_launch": int(b_k)}
-            rooflines[k]["traffic"], rooflines[k]["traffic_source"] = pmc_traffic(k)
-            if rooflines[k]["traffic"]:
-                rooflines[k]["frac_traffic"] = round(rooflines[k]["traffic"] / (ms_k / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
     rounds_per_s = args.steps / elapsed
     out = {
         "metric": "peer-message deliveries/sec + gossipsub rounds/sec (node), 1M peers 64 topics",
@@ -597,11 +652,13 @@ def main():
         # the oracle's reference mode roughly doubles iwant_sent on gossipsub_scored
         "schedule": "phase split: payload before control per hop (DESIGN.md 3a; per-RPC order ~2x iwant_sent)",
         "phase_a_reads": "frontier bitmaps" if eng.frontier_dense else "frontier lists",
-        "roofline": roofline,
-        "rooflines_other": rooflines,
-        "device_gib": device_gb,  # device memory the engine holds (free memory before / after its start)
         "setup_s": round(setup_s, 1),
     }
+    if args.full:
+        roofline, rooflines = roofline_report(args, eng, wl, kstats, events, c0, c1, hop0, prop_hops, partitioned)
+        out["roofline"] = roofline
+        out["rooflines_other"] = rooflines
+        out["device_gib"] = device_gb  # device memory the engine holds (free memory before / after its start)
     if args.lib:
         out["experiment_lib"] = os.path.basename(args.lib)
     if args.rpc_accounting:
@@ -613,7 +670,7 @@ def main():
                            "rank0_host_ms_per_step": round((x1[0] - x0[0]) / args.steps, 3),
                            "rank0_bytes_in_per_step": (x1[1] - x0[1]) // args.steps,
                            "rank0_nodes": eng.node_range[1] - eng.node_range[0]}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(wl)
     print(json.dumps(out))
     if dist is not None:

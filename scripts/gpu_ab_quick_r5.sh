@@ -11,7 +11,7 @@ B="go-libp2p-pubsub_amd/build"
 run() {  # name lib workload
   local lib=""
   [ "$2" = main ] || lib="--lib $B/libgossip_engine_var_$2.so"
-  timeout -k 10 300 python -u bench.py --workload "$3" --steps 20 --warmup 5 --no-cpu-baseline $lib \
+  timeout -k 10 300 python -u bench.py --full --workload "$3" --steps 20 --warmup 5 --no-cpu-baseline $lib \
       > "$OUT/$1.json" 2> "$OUT/$1.err"
 }
 for wl in config4 config3 config5; do

@@ -9,18 +9,18 @@ shift
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 B="go-libp2p-pubsub_amd/build"
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c4.json" 2> "$OUT/main_c4.err" &&
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c4.json" 2> "$OUT/main_c4.err" &&
 for v in "$@"; do
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --lib "$B/libgossip_engine_var_$v.so" \
+  timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --lib "$B/libgossip_engine_var_$v.so" \
       > "$OUT/${v}_c4.json" 2> "$OUT/${v}_c4.err" || exit 1
 done &&
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c4_again.json" 2> "$OUT/main_c4_again.err" &&
-timeout -k 10 300 python -u bench.py --workload config3 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c3.json" 2> "$OUT/main_c3.err" &&
-timeout -k 10 300 python -u bench.py --workload config5 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c5.json" 2> "$OUT/main_c5.err" &&
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c4_again.json" 2> "$OUT/main_c4_again.err" &&
+timeout -k 10 300 python -u bench.py --full --workload config3 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c3.json" 2> "$OUT/main_c3.err" &&
+timeout -k 10 300 python -u bench.py --full --workload config5 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_c5.json" 2> "$OUT/main_c5.err" &&
 for v in "$@"; do
-  timeout -k 10 300 python -u bench.py --workload config5 --steps 5 --warmup 5 --no-cpu-baseline \
+  timeout -k 10 300 python -u bench.py --full --workload config5 --steps 5 --warmup 5 --no-cpu-baseline \
       --lib "$B/libgossip_engine_var_$v.so" > "$OUT/${v}_c5.json" 2> "$OUT/${v}_c5.err" || exit 1
-  timeout -k 10 300 python -u bench.py --workload config3 --steps 20 --warmup 5 --no-cpu-baseline \
+  timeout -k 10 300 python -u bench.py --full --workload config3 --steps 20 --warmup 5 --no-cpu-baseline \
       --lib "$B/libgossip_engine_var_$v.so" > "$OUT/${v}_c3.json" 2> "$OUT/${v}_c3.err" || exit 1
 done &&
 echo done

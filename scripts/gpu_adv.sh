@@ -7,6 +7,6 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
     > "$OUT/pytest_gpu.log" 2>&1 &&
-timeout -k 10 900 python -u bench.py --workload config5 --steps 3 --warmup 2 \
+timeout -k 10 900 python -u bench.py --full --workload config5 --steps 3 --warmup 2 \
     > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" &&
 echo done

@@ -6,9 +6,9 @@ OUT=gpurun_out/${1:-expb}
 shift
 mkdir -p "$OUT"
 for wl in config4 config3; do
-  timeout -k 10 300 python -u bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${wl}_product.json" 2>"$OUT/err.txt" || exit 1
+  timeout -k 10 300 python -u bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${wl}_product.json" 2>"$OUT/err.txt" || exit 1
   for lib in "$@"; do
-    timeout -k 10 300 python -u bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline \
       --lib go-libp2p-pubsub_amd/build/$lib > "$OUT/${wl}_$lib.json" 2>>"$OUT/err.txt" || exit 1
   done
 done

@@ -12,5 +12,5 @@ if [ -n "$2" ]; then K=(-k "$2"); fi
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "${K[@]}" \
     > "$OUT/pytest_gpu.log" 2>&1 &&
 GS_STAMPS_LIB=libgossip_engine_var_stamps.so timeout -k 10 240 python3 -u scripts/stamps.py config4 > "$OUT/stamps_config4.txt" 2>&1 &&
-timeout -k 10 600 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" &&
+timeout -k 10 600 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" &&
 echo done

@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
     > "$OUT/pytest_gpu.log" 2>&1 &&
 GS_DIST_BACKEND=gloo timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 --peers 100000 \
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 2 --warmup 1 --peers 100000 \
     > "$OUT/bench_p2.json" 2> "$OUT/bench_p2.err" &&
-timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --peers 100000 --no-cpu-baseline \
+timeout -k 10 300 python -u bench.py --full --steps 2 --warmup 1 --peers 100000 --no-cpu-baseline \
     > "$OUT/bench_p1.json" 2> "$OUT/bench_p1.err" &&
 echo done

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/${1:-r5n}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+B="timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
     > "$OUT/pytest_gpu.log" 2>&1 &&
 $B --workload config5 > "$OUT/c5_dropbuf.json" 2> "$OUT/c5_dropbuf.err" &&

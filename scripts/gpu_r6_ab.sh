@@ -15,9 +15,9 @@ if [ "$TESTS" != "none" ]; then
   tail -3 "$OUT/pytest.log"
 fi
 for wl in config4 config3; do
-  timeout -k 10 300 python -u bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_$wl.json" 2> "$OUT/main_$wl.err" || exit 1
+  timeout -k 10 300 python -u bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/main_$wl.json" 2> "$OUT/main_$wl.err" || exit 1
   for v in "$@"; do
-    timeout -k 10 300 python -u bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu-baseline \
         --lib "$B/libgossip_engine_var_$v.so" > "$OUT/${v}_$wl.json" 2> "$OUT/${v}_$wl.err" || exit 1
   done
 done

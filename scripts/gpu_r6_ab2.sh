@@ -15,7 +15,7 @@ for wl in config4 config3; do
 for v in new prev new prev; do
   lib=go-libp2p-pubsub_amd/build/libgossip_engine.so
   [ "$v" = prev ] && lib=go-libp2p-pubsub_amd/build/libgossip_engine_var_prev.so
-  timeout -k 10 300 python -u bench.py --workload $wl --no-cpu-baseline --steps 10 --warmup 3 --lib "$lib" \
+  timeout -k 10 300 python -u bench.py --full --workload $wl --no-cpu-baseline --steps 10 --warmup 3 --lib "$lib" \
       > "$OUT/bench_${wl}_$v.json" 2> "$OUT/bench_${wl}_$v.err" || exit 1
   python -c "import json,sys; j=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=j['kernel_ms_per_step']; print(sys.argv[2], round(j['value']/1e9,3), k)" "$OUT/bench_${wl}_$v.json" "$wl $v"
 done

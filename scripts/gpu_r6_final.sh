@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
     > "$OUT/pytest_gpu.log" 2>&1 &&
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT/smoke.log" 2>&1 &&
-timeout -k 10 300 python -u bench.py --workload config3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" &&
+timeout -k 10 300 python -u bench.py --full --workload config3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" &&
 echo done
 rc=$?
 tail -2 "$OUT/pytest_gpu.log"

@@ -6,6 +6,6 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/${1:-r6_final3}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 400 python3 -u bench.py --workload config3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" &&
-timeout -k 10 400 python3 -u bench.py --workload config5 --steps 5 --warmup 2 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" &&
+timeout -k 10 400 python3 -u bench.py --full --workload config3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" &&
+timeout -k 10 400 python3 -u bench.py --full --workload config5 --steps 5 --warmup 2 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" &&
 echo done

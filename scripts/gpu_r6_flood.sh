@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest -x -q -s --timeout 300 --timeout-method th
     tests/test_golden.py tests/test_parity_gpu.py tests/test_scale_gpu.py -k "floodsub or flood or scale" \
     > "$OUT/pytest.log" 2>&1 || { tail -30 "$OUT/pytest.log"; exit 1; }
 tail -3 "$OUT/pytest.log"
-timeout -k 10 300 python -u bench.py --workload config2 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_config2.json" 2> "$OUT/bench_config2.err" || exit 1
+timeout -k 10 300 python -u bench.py --full --workload config2 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_config2.json" 2> "$OUT/bench_config2.err" || exit 1
 python - "$OUT" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1] + "/bench_config2.json").read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ tail -1 "$OUT/pytest.log"
 for v in new head new head; do
   lib=go-libp2p-pubsub_amd/build/libgossip_engine.so
   [ "$v" = head ] && lib=go-libp2p-pubsub_amd/build/libgossip_engine_var_headhb.so
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 10 --warmup 3 --lib "$lib" \
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 10 --warmup 3 --lib "$lib" \
       > "$OUT/bench_c4_$v.json" 2> "$OUT/bench_c4_$v.err" || exit 1
   python -c "import json,sys; j=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=j['kernel_ms_per_step']; print(sys.argv[2], round(j['value']/1e9,3), 'hb', k['heartbeat'], 'pa', k['phase_a'])" "$OUT/bench_c4_$v.json" $v
 done

@@ -14,7 +14,7 @@ tail -1 "$OUT/pytest_gpu.log"
 for v in new prev new prev; do
   lib=go-libp2p-pubsub_amd/build/libgossip_engine.so
   [ "$v" = prev ] && lib=go-libp2p-pubsub_amd/build/libgossip_engine_var_prev.so
-  timeout -k 10 300 python -u bench.py --workload config2_rs100 --no-cpu-baseline --steps 3 --warmup 1 --lib "$lib" \
+  timeout -k 10 300 python -u bench.py --full --workload config2_rs100 --no-cpu-baseline --steps 3 --warmup 1 --lib "$lib" \
       > "$OUT/bench_rs_$v.json" 2> "$OUT/bench_rs_$v.err" || exit 1
   python -c "import json,sys; j=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(j['value']/1e9,3), j['kernel_ms_per_step'])" "$OUT/bench_rs_$v.json" $v
 done

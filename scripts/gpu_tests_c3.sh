@@ -7,6 +7,6 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
     > "$OUT/pytest_gpu.log" 2>&1 &&
-timeout -k 10 600 python -u bench.py --workload config3 --steps 3 --warmup 2 --no-cpu-baseline \
+timeout -k 10 600 python -u bench.py --full --workload config3 --steps 3 --warmup 2 --no-cpu-baseline \
     > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" &&
 echo done
