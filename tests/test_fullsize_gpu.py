@@ -164,7 +164,7 @@ def test_config3_full_size_with_ihave_cuts(olib):
     wl = bench.WORKLOADS["config3"]
     rounds = 9
     e, _ = bench.build_engine(wl, rounds, 3, 0)
-    # the engine's cut-mode bound (gs_engine.hip stepOne): messages published
+    # the engine's cut-mode bound (gs_engine.hip phaseB): messages published
     # within HistoryGossip + 1 heartbeats plus the delivery age bound
     per_hop = bench.MSGS_PER_ROUND // H
     window = (5 + 1) * H + 3 * H + 2

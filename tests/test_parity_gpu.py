@@ -30,6 +30,63 @@ def test_gpu_stepwise_equals_one_call(oracle_path):
     assert scenarios.compare(scenarios.snapshot(e1, ids), scenarios.snapshot(e2, ids)) == []
 
 
+def _dense_1200(lib, batches):
+    """gossipsub_dense's network with one message per hop from hop 20, 1200 in
+    all, published in `batches` (lists of index ranges) with the engine stepped
+    up to each batch's first hop in between; the last 100 messages' snapshot
+    (older slots are recycled: 256 slots, at most 100 live)."""
+    from pubsub_amd import NewGossipSub, WithHop, WithMessageWindow, WithRecordDeliveries, WithSeed, graphs
+    n = 20
+    e = NewGossipSub(n, 1, graphs.dense_connect(n, 1), graphs.all_subscribed(n, 1), WithRecordDeliveries(),
+                     WithSeed(1), WithHop(scenarios.HOP), WithMessageWindow(256), lib=lib)
+    src, top, hops = scenarios._publish_schedule(n, 1, 1200, 20, 1, 1)
+    done = 0
+    for lo, hi in batches:
+        if lo:
+            e.step(int(hops[lo - 1]) + 1 - done)
+            done = int(hops[lo - 1]) + 1
+        e.publish(src[lo:hi], top[lo:hi], hops[lo:hi])
+    e.step(int(hops[-1]) + 40 - done)
+    return scenarios.snapshot(e, range(1100, 1200))
+
+
+def test_gpu_batched_publish_equals_one_publish(oracle_path):
+    """Publishing after the first step appends to the device's message arrays;
+    the third batch takes them from 600 to 1200 entries, past their first
+    capacity of 1024, so they are reallocated and uploaded again mid-run.  The
+    result equals the same schedule published in one call."""
+    once = [(0, 1200)]
+    ref = _dense_1200(oracle_path, once)
+    got = _dense_1200(PRODUCT_LIB, [(0, 300), (300, 600), (600, 1200)])
+    bad = scenarios.compare(ref, got)
+    assert bad == [], "\n".join(bad)
+    bad = scenarios.compare(_dense_1200(PRODUCT_LIB, once), got)
+    assert bad == [], "\n".join(bad)
+
+
+def test_gpu_start_refusal_is_repeatable(oracle_path):
+    """A start() that refuses its parameters (GossipRetransmission > 253, a
+    host-side check) leaves nothing behind: the next step refuses in the same
+    words, and after the engine is destroyed a valid one runs as usual."""
+    from pubsub_amd import (GossipEngineError, NewGossipSub, WithGossipSubParams, WithHop, WithMessageWindow,
+                            WithSeed, _abi, graphs)
+    p = scenarios.GossipSubParams()
+    p.GossipRetransmission = 254
+    n = 20
+    e = NewGossipSub(n, 1, graphs.dense_connect(n, 1), graphs.all_subscribed(n, 1), WithSeed(1),
+                     WithHop(scenarios.HOP), WithMessageWindow(256), WithGossipSubParams(p), lib=PRODUCT_LIB)
+    said = []
+    for _ in range(2):
+        with pytest.raises(GossipEngineError) as ei:
+            e.step(1)
+        assert ei.value.code == _abi.GS_EUNSUPPORTED
+        said.append(str(ei.value))
+    assert said[0] == said[1] and "GossipRetransmission" in said[0]
+    e.close()
+    bad = scenarios.compare(scenarios.run(oracle_path, "gossipsub_dense"), scenarios.run(PRODUCT_LIB, "gossipsub_dense"))
+    assert bad == [], "\n".join(bad)
+
+
 def _retuned(lib):
     """Topic.SetScoreParams mid-run (score.go:192-232): topic 1 gets lower
     first/mesh delivery caps (the recap clamps existing counters) and new
