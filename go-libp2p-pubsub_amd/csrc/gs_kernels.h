@@ -445,9 +445,11 @@ __global__ __launch_bounds__(64) void k_fanout_pub(Dev d, const int32_t* __restr
     const uint64_t key = gs_key64(d.seed, GS_SITE_GP_FANOUT_PUB, u, (uint32_t)hop, v, t);
     const bool sel = select_k(cand, key, d.D);
     const unsigned long long any = __ballot(sel);
+    // (a node publishing to two unjoined topics in one hop has two waves on
+    // its row: each sets its own topic's bit only)
     if (any) {
-      if (valid) d.fanout[e] = sel ? (fo | (1ull << t)) : fo;
-      if (lane == 0) d.fanoutPresent[u] |= 1ull << t;
+      if (sel) atomicOr((unsigned long long*)&d.fanout[e], 1ull << t);
+      if (lane == 0) atomicOr((unsigned long long*)&d.fanoutPresent[u], 1ull << t);
     }
   }
   if (lane == 0) d.lastpub[(int64_t)u * d.T + t] = now;

@@ -108,5 +108,50 @@ def sparse_connect(n, seed):
     return connect_some(n, 3, seed)
 
 
+LADDER_HUBS = (64, 64, 63, 63, 62, 48, 33, 33, 32, 32, 31, 31)
+LADDER32_HUBS = (32, 32, 31, 17, 16)
+
+
+def degree_ladder(n, seed, hubs=LADDER_HUBS, pendant=4, isolated=2, body_dials=3, max_degree=None):
+    """Every degree class of the one-wave-per-node kernels in one graph: nodes
+    0..len(hubs)-1 are hubs with exactly the given degrees (hubs 0 and 1 are
+    connected to each other, every other hub neighbour is a body node drawn
+    without replacement), each body node dials `body_dials` random other body
+    nodes (connectSome among the body), the last `isolated` nodes have no
+    edges and the `pendant` nodes before them exactly one, to a body node.
+    The dialer of every pair is drawn from the seeded generator.  Raises if
+    the body is too small for a hub, or if `max_degree` is given and a node
+    ends above it (LADDER32_HUBS with max_degree=32 keeps the graph inside
+    the half-wave kernels)."""
+    rng = np.random.default_rng(seed)
+    nh = len(hubs)
+    body = np.arange(nh, n - pendant - isolated)
+    if len(body) < 2 or body_dials >= len(body):
+        raise ValueError(f"degree_ladder: a body of {len(body)} nodes is too small")
+    pairs = set()
+    if nh >= 2:
+        pairs.add((0, 1))
+    for h, deg in enumerate(hubs):
+        need = deg - (1 if h < 2 and nh >= 2 else 0)
+        if need < 0 or need > len(body):
+            raise ValueError(f"degree_ladder: hub {h} cannot reach degree {deg} with a body of {len(body)} nodes")
+        for v in rng.choice(body, need, replace=False):
+            pairs.add((h, int(v)))
+    for u in body:
+        others = body[body != u]
+        for v in rng.choice(others, body_dials, replace=False):
+            pairs.add((min(int(u), int(v)), max(int(u), int(v))))
+    for p in range(n - pendant - isolated, n - isolated):
+        pairs.add((int(rng.choice(body)), p))
+    pairs = np.array(sorted(pairs), dtype=np.int64)
+    flip = rng.random(len(pairs)) < 0.5
+    pairs[flip] = pairs[flip][:, ::-1]
+    g = _to_csr(n, pairs)
+    deg = np.diff(g[0])
+    if max_degree is not None and deg.max() > max_degree:
+        raise ValueError(f"degree_ladder: node {int(deg.argmax())} has degree {int(deg.max())} > {max_degree}")
+    return g
+
+
 def all_subscribed(n, topics):
     return np.full(n, (1 << topics) - 1 if topics < 64 else 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)

@@ -22,6 +22,21 @@ def _publish_schedule(n, topics, count, start, every, seed, srcs=None):
     return src.astype(np.int32), top.astype(np.int32), np.asarray(hops, dtype=np.int64)
 
 
+def _graph(graph, n, k, seed):
+    """(n, graph): the given CSR triple, or today's random regular graph."""
+    if graph is None:
+        return n, graphs.random_regular(n, k, seed)
+    return len(graph[0]) - 1, graph
+
+
+def _set_authors(src, authors, ok=None):
+    """Gives len(authors) messages spread evenly over the schedule (over the
+    ones with `ok` set) to the given nodes, in place."""
+    idx = np.arange(len(src)) if ok is None else np.flatnonzero(ok)
+    for i, a in enumerate(authors):
+        src[idx[(i + 1) * len(idx) // (len(authors) + 1)]] = a
+
+
 def floodsub_dense(lib, seed=1, extra=()):
     """TestFloodsubDense-like: 20 hosts, denseConnect, 100 messages."""
     n = 20
@@ -33,12 +48,14 @@ def floodsub_dense(lib, seed=1, extra=()):
     return e, int(hops[-1]) + 20
 
 
-def floodsub_multitopic(lib, n=300, k=12, topics=3, seed=4, msgs=240, extra=()):
+def floodsub_multitopic(lib, n=300, k=12, topics=3, seed=4, msgs=240, extra=(), graph=None, authors=()):
     """floodsub.go:76-100 with several topics and partial subscriptions: hosts
     forward only their own topics' messages, to the peers subscribed to them,
     and publish to topics they may not be subscribed to (floodsub's Publish
-    needs no subscription).  A dense-frontier engine (k_flood_a) on one GPU."""
-    g = graphs.random_regular(n, k, seed)
+    needs no subscription).  A dense-frontier engine (k_flood_a) on one GPU.
+    graph: a CSR triple instead of the random regular graph (n follows it);
+    authors: nodes that each get one of the scheduled messages."""
+    n, g = _graph(graph, n, k, seed)
     rng = np.random.default_rng(seed)
     subs = np.zeros(n, dtype=np.uint64)
     for t in range(topics):
@@ -46,16 +63,20 @@ def floodsub_multitopic(lib, n=300, k=12, topics=3, seed=4, msgs=240, extra=()):
     e = NewFloodSub(n, topics, g, subs, WithRecordDeliveries(), WithSeed(seed), WithMessageWindow(128), *extra,
                     lib=lib)
     src, top, hops = _publish_schedule(n, topics, msgs, 1, 1, seed + 1)
+    _set_authors(src, authors)
     e.publish(src, top, hops)
+    e.sched_src, e.sched_hops = src, hops
     return e, int(hops[-1]) + 20
 
 
-def randomsub(lib, size, n=200, k=16, seed=2, msgs=60, extra=()):
-    g = graphs.random_regular(n, k, seed)
+def randomsub(lib, size, n=200, k=16, seed=2, msgs=60, extra=(), graph=None, authors=()):
+    n, g = _graph(graph, n, k, seed)
     e = NewRandomSub(n, 1, g, graphs.all_subscribed(n, 1), size, WithRecordDeliveries(), WithSeed(seed),
                      WithMessageWindow(128), *extra, lib=lib)
     src, top, hops = _publish_schedule(n, 1, msgs, 0, 1, seed)
+    _set_authors(src, authors)
     e.publish(src, top, hops)
+    e.sched_src, e.sched_hops = src, hops
     return e, int(hops[-1]) + 20
 
 
@@ -73,14 +94,16 @@ def gossipsub_dense(lib, seed=1, msgs=100, extra=()):
 
 def gossipsub_scored(lib, n=300, k=20, topics=1, seed=3, msgs=300, hb=12, flood=False, sub_frac=1.0,
                      app_neg_frac=0.0, ip_groups=0, params=None, window=1024, extra=(), app_neg=-150.0,
-                     direct_frac=0.0, topic0_frac=0.0, burst=None):
+                     direct_frac=0.0, topic0_frac=0.0, burst=None, graph=None, authors=()):
     """gossipsub v1.1 with Eth2-derived scoring over a random regular graph.
     window = slots_per_topic; direct_frac: fraction of the undirected edges
     made direct peers on both ends (WithDirectPeers); topic0_frac: fraction of
     the messages forced onto topic 0; burst = (node, count, hop): `count` more
-    messages by `node` at `hop`, on random topics."""
+    messages by `node` at `hop`, on random topics; graph: a CSR triple instead
+    of the random regular graph (n follows it); authors: nodes that each get
+    one of the scheduled messages."""
     rng = np.random.default_rng(seed)
-    g = graphs.random_regular(n, k, seed)
+    n, g = _graph(graph, n, k, seed)
     if direct_frac:
         rowptr, col, _ = g
         src = np.repeat(np.arange(n), np.diff(rowptr))
@@ -120,6 +143,7 @@ def gossipsub_scored(lib, n=300, k=20, topics=1, seed=3, msgs=300, hb=12, flood=
     if topic0_frac:
         top[rng2.random(msgs) < topic0_frac] = 0
     hops = (5 + (np.arange(msgs) * (hb * 10 - 20)) // msgs).astype(np.int64)
+    _set_authors(src, authors)
     if burst is not None:
         bn, bc, bh = burst
         src = np.concatenate([src, np.full(bc, bn, np.int32)])
@@ -129,7 +153,7 @@ def gossipsub_scored(lib, n=300, k=20, topics=1, seed=3, msgs=300, hb=12, flood=
         src, top, hops = src[order], top[order], hops[order]
         msgs += bc
     e.publish(src, top, hops)
-    e.sched_top, e.sched_hops = top, hops
+    e.sched_src, e.sched_top, e.sched_hops = src, top, hops
     st = window
     if msgs > st:
         # the engine reads back only messages whose slot is not recycled yet:
@@ -396,17 +420,20 @@ def sinkhole(lib, extra=()):
 
 
 def adversarial_mix(lib, n=400, k=16, seed=51, sybil_frac=0.2, queue=6, msgs=600, hb=10, gater=True,
-                    window=2048, churn=0, retain=None, px=0.0, extra=()):
+                    window=2048, churn=0, retain=None, px=0.0, extra=(), graph=None, authors=()):
     """A config-5-like mix: 20% Sybils split over IWANT spam,
     GRAFT spam, phantom-IHAVE spam and invalid-message publishing, 20 Sybils
     per shared IP (P6), the peer gater, topic validator with a bounded queue,
     Eth2 scoring.  churn: connections going down per 3 hops (each back after
     5-40 hops); retain: the gater's RetainStats; px: peer exchange on, with
     this fraction of the connections starting down (PX dials bring them up;
-    pxConnect's PrunePeers truncation, gossipsub.go:856-905)."""
+    pxConnect's PrunePeers truncation, gossipsub.go:856-905).  graph: a CSR
+    triple instead of the random regular graph (n follows it); authors: honest
+    nodes that each get one of the valid messages."""
     rng = np.random.default_rng(seed)
-    g = graphs.random_regular(n, k, seed)
+    n, g = _graph(graph, n, k, seed)
     sybil = rng.random(n) < sybil_frac
+    sybil[list(authors)] = False
     ids = np.flatnonzero(sybil)
     beh = np.zeros(n, np.uint8)
     kind_of = rng.integers(0, 4, len(ids))        # 0 IWANT spam, 1 GRAFT spam, 2 phantom IHAVE, 3 invalid
@@ -458,8 +485,10 @@ def adversarial_mix(lib, n=400, k=16, seed=51, sybil_frac=0.2, queue=6, msgs=600
         sel = (r >= 1 / 3) & (r < 0.5)
         src[sel] = rng.choice(ph, int(sel.sum()))
         kind[sel] = GS_MSG_PHANTOM
+    _set_authors(src, authors, kind == 0)
     e.publish(src, np.zeros(msgs, np.int32), hops, kind=kind)
     e.sybil = sybil
+    e.sched_src, e.sched_hops = src, hops
     return e, hb * 10 + 5
 
 
@@ -576,12 +605,14 @@ def churn_graft(lib, extra=()):
     return e, 170
 
 
-def churn_scored(lib, n=240, k=16, topics=2, seed=65, msgs=400, hb=14, extra=()):
+def churn_scored(lib, n=240, k=16, topics=2, seed=65, msgs=400, hb=14, extra=(), graph=None, authors=()):
     """A scored mix: 15% negative app scores and shared IPs (retained vs dropped
     records, P6 recounted), random connections going down and coming back,
-    topics left and re-joined, Eth2 scoring with a RetainScore of 2 s."""
+    topics left and re-joined, Eth2 scoring with a RetainScore of 2 s.
+    graph: a CSR triple instead of the random regular graph (n follows it);
+    authors: nodes that each get one of the scheduled messages."""
     rng = np.random.default_rng(seed)
-    g = graphs.random_regular(n, k, seed)
+    n, g = _graph(graph, n, k, seed)
     subs = graphs.all_subscribed(n, topics)
     sp = eth2_peer_score_params(topics)
     sp.RetainScore = 2 * Second
@@ -607,7 +638,9 @@ def churn_scored(lib, n=240, k=16, topics=2, seed=65, msgs=400, hb=14, extra=())
     src = rng.integers(0, n, msgs).astype(np.int32)
     top = rng.integers(0, topics, msgs).astype(np.int32)
     hops = (5 + (np.arange(msgs) * (hb * 10 - 20)) // msgs).astype(np.int64)
+    _set_authors(src, authors)
     e.publish(src, top, hops)
+    e.sched_src, e.sched_hops = src, hops
     return e, hb * 10 + 5
 
 
@@ -818,7 +851,8 @@ def mixed_routers(n, seed, flood=0.15, v10=0.15, rs=0.10):
     return routers
 
 
-def mixed_scored(lib, n=300, k=20, topics=3, seed=82, msgs=300, hb=12, px=True, extra=()):
+def mixed_scored(lib, n=300, k=20, topics=3, seed=82, msgs=300, hb=12, px=True, extra=(), graph=None,
+                 authors=()):
     """A scored mixed network: 15% floodsub, 15% gossipsub-v1.0-only and 10%
     randomsub (size 50) hosts among gossipsub v1.1 ones, 3 topics with 70%
     subscription (publishes to unjoined topics use fanout), negative app
@@ -826,9 +860,11 @@ def mixed_scored(lib, n=300, k=20, topics=3, seed=82, msgs=300, hb=12, px=True, 
     non-mesh peers only at score >= PublishThreshold (gossipsub.go:969-975).
     PX on with 10% of the connections starting down: v1.0 peers get PRUNEs
     without PX and backoff (gossipsub.go:1804-1807), PX lists hold
-    mesh-capable peers only (getPeers, :1849)."""
+    mesh-capable peers only (getPeers, :1849).  graph: a CSR triple instead of
+    the random regular graph (n follows it); authors: nodes that each get one
+    of the scheduled messages."""
     rng = np.random.default_rng(seed)
-    g = graphs.random_regular(n, k, seed)
+    n, g = _graph(graph, n, k, seed)
     rowptr, col, _ = g
     routers = mixed_routers(n, seed)
     subs = np.zeros(n, dtype=np.uint64)
@@ -852,23 +888,29 @@ def mixed_scored(lib, n=300, k=20, topics=3, seed=82, msgs=300, hb=12, px=True, 
     src = rng2.integers(0, n, msgs).astype(np.int32)
     top = rng2.integers(0, topics, msgs).astype(np.int32)
     hops = (5 + (np.arange(msgs) * (hb * 10 - 20)) // msgs).astype(np.int64)
+    _set_authors(src, authors)
     e.publish(src, top, hops)
     e.routers_h = routers
+    e.sched_src, e.sched_hops = src, hops
     return e, hb * 10 + 5
 
 
-def mixed_randomsub(lib, n=200, k=16, seed=83, msgs=60, extra=()):
+def mixed_randomsub(lib, n=200, k=16, seed=83, msgs=60, extra=(), graph=None, authors=()):
     """randomsub.go:99-160 in a network where 30% of the hosts run floodsub:
     a randomsub host always forwards to its floodsub-protocol topic peers and
-    samples max(6, ceil(sqrt(100))) = 10 of its randomsub-protocol ones."""
-    g = graphs.random_regular(n, k, seed)
+    samples max(6, ceil(sqrt(100))) = 10 of its randomsub-protocol ones.
+    graph: a CSR triple instead of the random regular graph (n follows it);
+    authors: nodes that each get one of the scheduled messages."""
+    n, g = _graph(graph, n, k, seed)
     routers = np.where(np.random.default_rng(seed).random(n) < 0.3, GS_ROUTER_FLOODSUB,
                        GS_ROUTER_RANDOMSUB).astype(np.uint8)
     e = NewRandomSub(n, 1, g, graphs.all_subscribed(n, 1), 100, WithRouters(routers), WithRecordDeliveries(),
                      WithSeed(seed), WithMessageWindow(128), *extra, lib=lib)
     src, top, hops = _publish_schedule(n, 1, msgs, 0, 1, seed)
+    _set_authors(src, authors)
     e.publish(src, top, hops)
     e.routers_h = routers
+    e.sched_src, e.sched_hops = src, hops
     return e, int(hops[-1]) + 20
 
 
@@ -884,3 +926,97 @@ MIXED = {
     "mixed_scored_4t": lambda lib, x=(): mixed_scored(lib, topics=4, seed=85, msgs=400, extra=x),
 }
 SCENARIOS.update(MIXED)
+
+
+# ---------------------------------------------------------------- degree ladder
+# Every degree from 0 to 64 in one run (graphs.degree_ladder, n = 160): hubs of
+# degree 64, 64, 63, 63, 62, 48, 33, 33, 32, 32, 31, 31 (nodes 0-11, hubs 0 and
+# 1 adjacent), a body of degree ~4-17, four pendant nodes (154-157) and two
+# isolated ones (158, 159).  The kernels run one wave per node with one lane
+# per neighbour and choose by degree: k_phase_a's pair2 (deg <= 32: rs_select2,
+# else rs_select), k_heartbeat<PAIR> (maxDeg <= 32) and the T * maxDeg phase-A
+# counters; the regular graphs above give every block the same lane mask.
+# Every schedule has a message by hub 0, by a pendant and by an isolated node.
+# "age" is the oracle's largest first-delivery hop - publish hop; "t" its run
+# time.  tests/test_ladder.py keeps the age 10 hops inside the engine's message
+# window (gs_engine.h setWindow): <= 20 where the window is 3 heartbeats,
+# <= 100 for ladder_churn (scheduled events widen the window to 11
+# heartbeats: a host that re-joins a topic catches up through gossip, so ages
+# past 30 hops are the scenario's point; churn_scored itself reaches 46).
+LADDER_N = 160
+LADDER_AUTHORS = (0, 154, 158)  # a degree-64 hub, a pendant node, an isolated node
+_ladder_cache = {}
+
+
+def ladder_graph(cap32=False):
+    """The ladder (seed 97); cap32: hubs of degree 32, 32, 31, 17, 16 and no
+    node above 32, so the half-wave kernels run on irregular rows."""
+    if cap32 not in _ladder_cache:
+        _ladder_cache[cap32] = (graphs.degree_ladder(LADDER_N, 97, hubs=graphs.LADDER32_HUBS, max_degree=32)
+                                if cap32 else graphs.degree_ladder(LADDER_N, 97))
+    return _ladder_cache[cap32]
+
+
+def _lad(fn, *a, cap32=False, pre=(), **kw):
+    return lambda lib, x=(): fn(lib, *a, graph=ladder_graph(cap32), authors=LADDER_AUTHORS,
+                                extra=tuple(pre) + tuple(x), **kw)
+
+
+LADDER = {
+    # non-PAIR heartbeat and full-wave phase A / B, scored; Dhi pruning on the
+    # hubs (278 PRUNEs).  age 6, t 0.24 s
+    "ladder_scored": _lad(gossipsub_scored, topics=1, seed=31, msgs=300, hb=12, window=512),
+    # fanout from hubs, partial subscription on 64-lane rows.  age 6, t 0.17 s
+    # (seeds 33, 34 and 36 gave ages 45, 42 and 25: a body node whose few peers
+    # on a topic are all outside its mesh gets the message by gossip)
+    "ladder_multitopic": _lad(gossipsub_scored, topics=3, sub_frac=0.7, seed=35, msgs=240),
+    # k_push from a degree-64 sender: 40 messages x 64 peers > GS_PUSHR = 2048
+    # copies in one hop -> the -1 record path.  age 6, t 0.43 s
+    "ladder_4t_flood": _lad(gossipsub_scored, topics=4, flood=True, window=512, seed=35, burst=(0, 40, 40)),
+    # 32-bit phase-A counters with maxDeg 64.  age 7, t 0.87 s
+    "ladder_16t_wide": _lad(gossipsub_scored, topics=16, window=1024, topic0_frac=0.4, msgs=1200, hb=8, seed=37),
+    # nCnt = 4096, the non-PAIR heartbeat over 64 topics, k_refresh_rows /
+    # k_score_rows at 4096 pairs per node.  age 7, t 1.7 s
+    "ladder_64t": _lad(gossipsub_scored, topics=64, window=256, msgs=600, hb=8, seed=39),
+    # the same with 90% subscription.  age 6, t 1.1 s (sub_frac 0.8 gave ages
+    # 29-43 over seeds 41-44, sub_frac 0.9 gave 29, 21, 24 at seeds 42-44)
+    "ladder_64t_sub": _lad(gossipsub_scored, topics=64, window=256, msgs=600, hb=8, seed=41, sub_frac=0.9),
+    # PAIR heartbeat on irregular rows (degree 32, 1 and 0 in one run).  age 6,
+    # t 0.82 s
+    "ladder32_64t": _lad(gossipsub_scored, cap32=True, topics=64, window=256, msgs=600, hb=8, seed=43),
+    # rs_select (degree 33..64) and rs_select2 (degree <= 32) in one run; the
+    # target of 10 is below every hub's candidate count.  age 6 / 5, t 0.07 s
+    "ladder_randomsub_100": _lad(randomsub, 100),
+    "ladder_randomsub_N": _lad(randomsub, LADDER_N),
+    # the floodsub-peers-or-select_k branch at degree > 32.  age 5, t 0.08 s
+    "ladder_mixed_randomsub": _lad(mixed_randomsub),
+    # k_flood_a's bitmap path on 64-lane rows.  age 6, t 0.11 s
+    "ladder_floodsub_mt": _lad(floodsub_multitopic),
+    # ADV phase A / B, the gater and the validation queue with 64 senders per
+    # node (adversarial: the 11-heartbeat window; age 47).  t 0.34 s
+    "ladder_adversarial": _lad(adversarial_mix, seed=51),
+    # PX lists from degree-64 pruners, PrunePeers truncation (age 59).  t 0.26 s
+    "ladder_px_adversarial": _lad(adversarial_mix, seed=67, hb=12, px=0.15),
+    # k_edge_down / k_edge_up / k_p6 on full rows.  age 78, t 0.25 s
+    "ladder_churn": _lad(churn_scored),
+    # per-edge protocols on full rows, push filters.  age 7, t 0.18 s
+    "ladder_mixed_4t": _lad(mixed_scored, topics=4, seed=85, msgs=400),
+    # RPC byte accounting from 64-peer senders.  age 6, t 1.1 s
+    "acct_ladder_multitopic": _lad(gossipsub_scored, topics=3, sub_frac=0.7, seed=35, msgs=240, pre=(_acct(3),)),
+}
+SCENARIOS.update(LADDER)
+
+
+def degree65_star(lib, extra=()):
+    """A star whose centre has 65 leaves: one peer more than the engine's one
+    wave per node holds.  The reference's AddPeer has no bound (the oracle
+    runs it); the engine refuses the graph at its first step."""
+    leaves = 65
+    n = leaves + 1
+    rowptr = np.concatenate([[0, leaves], leaves + np.arange(1, leaves + 1)]).astype(np.int64)
+    col = np.concatenate([np.arange(1, n), np.zeros(leaves)]).astype(np.int32)
+    outbound = np.concatenate([np.ones(leaves), np.zeros(leaves)]).astype(np.uint8)
+    e = NewGossipSub(n, 1, (rowptr, col, outbound), graphs.all_subscribed(n, 1), WithRecordDeliveries(),
+                     WithFloodPublish(True), WithSeed(5), WithHop(HOP), WithMessageWindow(64), *extra, lib=lib)
+    e.publish(np.array([0, 7], np.int32), np.zeros(2, np.int32), np.array([12, 14], np.int64))
+    return e, 30

@@ -26,7 +26,9 @@ GOLDEN = json.load(open(os.path.join(HERE, "golden", "scenarios.json")))
 # graylisting + direct peers, Dhi pruning, slot recycling, config3's shape) and
 # floodsub; the adversarial / churn / PX / multi-topic ones use the lists
 DENSE = ["gossipsub_dense", "gossipsub_scored", "gossipsub_flood_publish", "gossipsub_negative_app",
-         "gossipsub_dense_dhi", "gossipsub_slot_reuse", "gossipsub_graylist_direct", "c3shape", "floodsub_dense"]
+         "gossipsub_dense_dhi", "gossipsub_slot_reuse", "gossipsub_graylist_direct", "c3shape", "floodsub_dense",
+         # several topics with partial subscriptions (k_flood_a), and 64-lane rows beside rows of 1 and 0
+         "floodsub_multitopic", "ladder_floodsub_mt", "ladder_scored"]
 LISTS_ONLY = ["gossipsub_multitopic", "adversarial_mix", "churn_scored"]
 
 

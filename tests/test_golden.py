@@ -31,7 +31,9 @@ def test_gpu_reproduces_golden(name):
 # Races show up as run-to-run differences before they show up as a wrong
 # digest: the scenarios with the most cross-lane LDS and global atomics in
 # phase B (IWANT serving, IHAVE handling, spam, cuts) run three more times.
-RACE_PRONE = ["gossipsub_dense_dhi", "c5shape", "adversarial_mix", "spam_ihave_2t", "churn_graft"]
+RACE_PRONE = ["gossipsub_dense_dhi", "c5shape", "adversarial_mix", "spam_ihave_2t", "churn_graft",
+              # full waves: 64 peers per node, 64 topics / 64 senders per validation queue
+              "ladder_64t", "ladder_adversarial"]
 
 
 @pytest.mark.gpu
@@ -47,7 +49,9 @@ def test_gpu_golden_repeatable(name):
 # entries within its cache window takes the rest in the rank's overflow table
 # (gs_set_peertx_capacity); the heartbeat's rebuild moves survivors back when
 # a node's own table has room.  The goldens must not move.
-PEERTX_SPILL = ["c3shape", "adversarial_mix", "gossipsub_slot_reuse", "churn_scored", "c4shape", "px_adversarial"]
+PEERTX_SPILL = ["c3shape", "adversarial_mix", "gossipsub_slot_reuse", "churn_scored", "c4shape", "px_adversarial",
+                # a host serving 64 peers from 4 slots spills at once
+                "ladder_scored"]
 
 
 @pytest.mark.gpu

@@ -3,6 +3,7 @@ same seeded scenarios, through the identical C-ABI calls.  Everything is
 compared bit-exactly: counters, per-(node, message) first-delivery hop and
 sender, mesh/fanout masks, backoff expiries, every float64 score counter and
 score (on their bit patterns, tolerance 0)."""
+import numpy as np
 import pytest
 
 import scenarios
@@ -84,6 +85,55 @@ def test_gpu_start_refusal_is_repeatable(oracle_path):
     assert said[0] == said[1] and "GossipRetransmission" in said[0]
     e.close()
     bad = scenarios.compare(scenarios.run(oracle_path, "gossipsub_dense"), scenarios.run(PRODUCT_LIB, "gossipsub_dense"))
+    assert bad == [], "\n".join(bad)
+
+
+def _fanout_all_topics(lib):
+    """Hosts 0-3 of gossipsub_dense's network have joined none of the 4 topics
+    and publish to all four in the same hop, every 7 hops: k_fanout_pub runs
+    four waves on one host's row at once (one per (host, topic) pair)."""
+    from pubsub_amd import NewGossipSub, WithHop, WithMessageWindow, WithRecordDeliveries, WithSeed, graphs
+    n, T = 20, 4
+    subs = graphs.all_subscribed(n, T)
+    subs[:4] = 0
+    e = NewGossipSub(n, T, graphs.dense_connect(n, 1), subs, WithRecordDeliveries(), WithSeed(1),
+                     WithHop(scenarios.HOP), WithMessageWindow(64), lib=lib)
+    hops = np.repeat(np.arange(12, 47, 7), 16).astype(np.int64)
+    src = np.tile(np.repeat(np.arange(4), T), 5).astype(np.int32)
+    top = np.tile(np.arange(T), 20).astype(np.int32)
+    e.publish(src, top, hops)
+    e.step(60)
+    return scenarios.snapshot(e, range(e.n_published))
+
+
+def test_gpu_fanout_to_several_topics_in_one_hop(oracle_path):
+    """Publish to several unjoined topics in one hop (gossipsub.go:977-994 per
+    message): every topic's fanout peers are kept, none lost to the others'
+    waves (ladder_mixed_4t found the lost update)."""
+    ref = _fanout_all_topics(oracle_path)
+    fo = ref["fanout"]
+    assert all(((fo >> np.uint64(t)) & np.uint64(1)).sum() > 0 for t in range(4))
+    for _ in range(3):
+        bad = scenarios.compare(ref, _fanout_all_topics(PRODUCT_LIB))
+        assert bad == [], "\n".join(bad)
+
+
+def test_gpu_degree_limit_refusal_is_repeatable(oracle_path):
+    """One wave per node: a node with 65 peers is refused on the host (the
+    oracle runs that graph, tests/test_ladder.py), in the same words each
+    time; after the engine is destroyed, a graph whose largest degree is
+    exactly 64 runs and equals the oracle."""
+    from pubsub_amd import GossipEngineError, _abi
+    e, _ = scenarios.degree65_star(PRODUCT_LIB)
+    said = []
+    for _ in range(2):
+        with pytest.raises(GossipEngineError) as ei:
+            e.step(1)
+        assert ei.value.code == _abi.GS_EUNSUPPORTED
+        said.append(str(ei.value))
+    assert said[0] == said[1] and "degree" in said[0]
+    e.close()
+    bad = scenarios.compare(scenarios.run(oracle_path, "ladder_scored"), scenarios.run(PRODUCT_LIB, "ladder_scored"))
     assert bad == [], "\n".join(bad)
 
 

@@ -149,6 +149,14 @@ def run_partitioned(world, name, oracle):
     (2, "randomsub_N"),
     (2, "mixed_randomsub"),
     (3, "mixed_scored_4t"),
+    # the degree ladder: rank 0 owns every hub (degree 31..64) and the last
+    # rank the pendant and isolated nodes, so the edge-balanced split is
+    # lopsided in nodes; traced nodes 0 and 3 are hubs of degree 64 and 63
+    (2, "ladder_scored"),
+    (3, "ladder_64t"),
+    (2, "ladder_randomsub_100"),
+    (3, "ladder_4t_flood"),
+    (2, "ladder_adversarial"),
 ])
 def test_partitioned_engine_matches_oracle(world, name, oracle_path):
     res = run_partitioned(world, name, oracle_path)

@@ -18,7 +18,16 @@ import scenarios
 from pubsub_amd import PRODUCT_LIB, WithEventTracer, _abi, encode_trace
 
 TRACED = [0, 3, 17, 42, 99, 150]
+# the degree ladder (scenarios.LADDER): hubs of degree 64, 33 and 32, a body
+# node, a pendant node and an isolated one
+LADDER_TRACED = [0, 6, 8, 42, 154, 158]
 T = _abi.TRACE_TYPES.index
+
+
+def traced_nodes(name):
+    if name.startswith("ladder_"):
+        return LADDER_TRACED
+    return [u for u in TRACED if u < 20] if name == "floodsub_dense" else [u for u in TRACED if u < 120]
 
 
 def traced_run(lib, name, nodes=TRACED, extra=()):
@@ -72,11 +81,15 @@ def check_invariants(e, ev, nodes):
 
 
 @pytest.mark.parametrize("name", ["gossipsub_scored", "gossipsub_multitopic", "floodsub_dense",
-                                  "gossipsub_dense_dhi", "acct_mixed"])
+                                  "gossipsub_dense_dhi", "acct_mixed", "ladder_scored", "ladder_multitopic"])
 def test_oracle_trace_invariants(oracle_path, name):
-    nodes = [u for u in TRACED if u < 20] if name == "floodsub_dense" else [u for u in TRACED if u < 120]
+    nodes = traced_nodes(name)
     e, ev = traced_run(oracle_path, name, nodes)
     check_invariants(e, ev, nodes)
+    if name.startswith("ladder_"):
+        deg = np.diff(e.rowptr)
+        assert [int(deg[u]) for u in nodes[:3] + nodes[4:]] == [64, 33, 32, 1, 0]
+        assert ((ev["node"] == nodes[5]) & (ev["type"] == T("ADD_PEER"))).sum() == 0
 
 
 # ---------------------------------------------------------------- encoder
@@ -214,9 +227,10 @@ def test_encode_round_trip_sizes(oracle_path):
 # ---------------------------------------------------------------- GPU parity
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["gossipsub_scored", "gossipsub_multitopic", "floodsub_dense",
-                                  "gossipsub_dense_dhi", "gossipsub_negative_app", "gossipsub_flood_publish", "acct_mixed"])
+                                  "gossipsub_dense_dhi", "gossipsub_negative_app", "gossipsub_flood_publish", "acct_mixed",
+                                  "ladder_scored", "ladder_multitopic"])
 def test_gpu_trace_equals_oracle(oracle_path, name):
-    nodes = [u for u in TRACED if u < 20] if name == "floodsub_dense" else [u for u in TRACED if u < 120]
+    nodes = traced_nodes(name)
     _, ref = traced_run(oracle_path, name, nodes)
     e, got = traced_run(PRODUCT_LIB, name, nodes)
     assert len(got) == len(ref), (len(got), len(ref))
