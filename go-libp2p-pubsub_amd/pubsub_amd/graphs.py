@@ -153,5 +153,26 @@ def degree_ladder(n, seed, hubs=LADDER_HUBS, pendant=4, isolated=2, body_dials=3
     return g
 
 
+def tailed(n_body, k, tail, seed):
+    """random_regular(n_body, k, seed) with a path of `tail` extra nodes hung on
+    body node 0: node n_body is connected to node 0, node n_body + i to node
+    n_body + i - 1, and the tip n_body + tail - 1 has degree 1.  A message
+    authored in the body reaches tail node i exactly one hop after node i - 1,
+    so the oldest first delivery of a run is set by `tail` (the message-window
+    edge scenarios).  The body keeps random_regular's edges and dialers; the
+    dialer of every tail pair is drawn from the seeded generator."""
+    if tail < 1:
+        raise ValueError("tailed: the tail needs at least one node")
+    rowptr, col, outbound = random_regular(n_body, k, seed)
+    src = np.repeat(np.arange(n_body, dtype=np.int64), np.diff(rowptr))
+    dialed = outbound == 1
+    body = np.stack([src[dialed], col[dialed].astype(np.int64)], axis=1)
+    chain = np.concatenate([[0], n_body + np.arange(tail, dtype=np.int64)])
+    path = np.stack([chain[:-1], chain[1:]], axis=1)
+    flip = np.random.default_rng(seed + 7919).random(tail) < 0.5  # (a longer tail keeps the shorter one's draws)
+    path[flip] = path[flip][:, ::-1]
+    return _to_csr(n_body + tail, np.concatenate([body, path]))
+
+
 def all_subscribed(n, topics):
     return np.full(n, (1 << topics) - 1 if topics < 64 else 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)

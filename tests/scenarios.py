@@ -1020,3 +1020,162 @@ def degree65_star(lib, extra=()):
                      WithFloodPublish(True), WithSeed(5), WithHop(HOP), WithMessageWindow(64), *extra, lib=lib)
     e.publish(np.array([0, 7], np.int32), np.zeros(2, np.int32), np.array([12, 14], np.int64))
     return e, 30
+
+
+# ---------------------------------------------------------------- message-window edge
+# The engine's seen-set is a fixed window of message slots (gs_engine.h
+# setWindow): a message must be first delivered within maxAge hops of its
+# publish, and its slot is used again no sooner than retireHops after it.  The
+# reference and the oracle have neither limit.  These runs sit on the limits:
+# graphs.tailed hangs a path on a small regular body, so a message written at
+# the tip (or in the body) is first delivered one hop later per tail node, and
+# the tail length alone sets the oracle's largest first-delivery age: maxAge
+# for the registered `_edge` member of a family, maxAge + 1 for its `_over`
+# member (WINDOW_OVER: the engine must refuse it, so it has no golden).
+# Authors alternate between a body node and the tail tip, one message per hop
+# and topic, so at every hop the tail carries a message of every age
+# 1..maxAge, young and old slots share 64-bit words and the in-flight set
+# straddles a word boundary.  One hop of the schedule carries slots - reuse
+# extra messages, so the first slots of every ring are used again exactly
+# `reuse` hops after their first use: the smallest distance gs_publish allows
+# when reuse == retireHops (tests/test_window.py checks that it is, that
+# `slots` is the smallest multiple of 64 the guard accepts, and the ages).
+# "t" is the oracle's run time of the _edge member.
+WIN_BODY = 24
+WIN_AUTHOR = 13  # the body author; the other author is the tail's tip
+
+
+def _win_params(hist=None):
+    if hist is None:
+        return None
+    p = GossipSubParams()
+    p.HistoryLength, p.HistoryGossip, p.HeartbeatInterval = hist
+    return p
+
+
+def window_engine(lib, router="gossipsub", k=12, tail=1, topics=1, slots=128, seed=101, partial=False,
+                  validate=False, event_at=None, hist=None, p3_after=None, extra=(), **_):
+    """The network of a window family, nothing published yet.  partial: the
+    body's subscriptions are drawn per topic as in floodsub_multitopic (node 0,
+    the body author and the tail take every topic); validate: an accepting
+    validator with an unbounded queue (the adversarial instantiation, the long
+    window); event_at: one scheduled disconnect of a body connection at that
+    hop (the long window through churnWindow); hist: (HistoryLength,
+    HistoryGossip, HeartbeatInterval); p3_after: MeshMessageDeliveriesActivation
+    (Eth2's 30 s would start the mesh-delivery penalties inside the long runs,
+    while the last messages still cross the tail: its pairs would prune each
+    other and the deliveries past them would wait for gossip)."""
+    g = graphs.tailed(WIN_BODY, k, tail, seed)
+    n = WIN_BODY + tail
+    subs = graphs.all_subscribed(n, topics)
+    if partial:
+        rng = np.random.default_rng(seed)
+        subs = np.zeros(n, dtype=np.uint64)
+        for t in range(topics):
+            subs[:WIN_BODY] |= (rng.random(WIN_BODY) < 0.6).astype(np.uint64) << np.uint64(t)
+        subs[[0, WIN_AUTHOR]] = graphs.all_subscribed(1, topics)[0]
+        subs[WIN_BODY:] = graphs.all_subscribed(1, topics)[0]
+    opts = [WithRecordDeliveries(), WithSeed(seed), WithMessageWindow(slots)]
+    if router == "floodsub":
+        e = NewFloodSub(n, topics, g, subs, *opts, *extra, lib=lib)
+    elif router == "randomsub":
+        e = NewRandomSub(n, topics, g, subs, 100, *opts, *extra, lib=lib)
+    else:
+        sp = eth2_peer_score_params(topics)
+        if p3_after is not None:
+            for tp in sp.Topics.values():
+                tp.MeshMessageDeliveriesActivation = p3_after
+        opts += [WithPeerScore(sp, eth2_thresholds()), WithHop(HOP)]
+        if hist is not None:
+            opts.append(WithGossipSubParams(_win_params(hist)))
+        if validate:
+            opts.append(WithValidation([1] * topics, 0))
+        e = NewGossipSub(n, topics, g, subs, *opts, *extra, lib=lib)
+        if event_at is not None:
+            a = WIN_AUTHOR
+            e.schedule_events([GS_EV_DISCONNECT], [a], [int(g[1][g[0][a]])], [event_at])
+    e.tip = n - 1
+    return e
+
+
+def window_schedule(tail, topics=1, slots=128, reuse=100, start=1, count=120, shared=False, **_):
+    """(src, topic, hop) of a window family: from hop `start`, `count` hops
+    with one message per topic (shared: one message over all topics, the topic
+    rotating), written by the body author and the tail's tip in turn; the
+    11th hop carries slots - reuse more per topic, so each ring's first 11
+    slots are used again exactly `reuse` hops after their first use."""
+    tip = WIN_BODY + tail - 1
+    src, top, hops = [], [], []
+    for i in range(count):
+        for t in ([i % topics] if shared else range(topics)):
+            for j in range(1 + (slots - reuse if i == 10 and not shared else 0)):
+                src.append(tip if (i + j + (0 if shared else t)) % 2 else WIN_AUTHOR)
+                top.append(t)
+                hops.append(start + i)
+    return np.array(src, np.int32), np.array(top, np.int32), np.array(hops, np.int64)
+
+
+def window_run(lib, fam, tail=None, extra=(), **over):
+    """(engine, hops) of family `fam` (a WINDOW_FAMILIES entry) with the given
+    tail (default: the family's _edge tail): the schedule published, the run
+    long enough for the last message to cross the tail."""
+    kw = dict(WINDOW_FAMILIES[fam], **over)
+    if tail is not None:
+        kw["tail"] = tail
+    e = window_engine(lib, extra=extra, **kw)
+    src, top, hops = window_schedule(**kw)
+    e.publish(src, top, hops)
+    e.sched_src, e.sched_top, e.sched_hops = src, top, hops
+    keep = []
+    for t in range(kw["topics"]):
+        keep += list(np.flatnonzero(top == t)[-kw["slots"]:])
+    e.snapshot_ids = sorted(int(i) for i in keep)
+    return e, int(hops[-1]) + kw["tail"] + 12
+
+
+# tail: the _edge member's (the oracle's largest first-delivery age == maxAge);
+# the _over member's is one more.  reuse == retireHops, slots the smallest
+# multiple of 64 >= reuse.
+WINDOW_FAMILIES = {
+    # floodsub, one topic: k_flood_a with the frontier bitmaps, the list walk
+    # without.  maxAge 48, retireHops 50
+    "win_flood": dict(router="floodsub", k=6, topics=1, slots=64, reuse=50, start=1, count=120, tail=45),
+    # three topics, partial subscriptions in the body (k_flood_a's topic masks)
+    "win_flood_3t": dict(router="floodsub", k=6, topics=3, partial=True, slots=64, reuse=50, start=1, count=120,
+                         tail=44),
+    # randomsub with a target of max(6, ceil(sqrt(100))) = 10 peers: the tail
+    # (degree <= 2) sends to all, and so does the body (degree 8, node 0 with
+    # the tail 9): a body that selected would now and then leave the tail out
+    "win_randomsub": dict(router="randomsub", k=8, topics=1, slots=64, reuse=50, start=1, count=120, tail=46),
+    # gossipsub, one topic, Eth2 scoring, published once the mesh has formed;
+    # degree 12 in the body, so IHAVE / IWANT are live.  maxAge 30, retireHops
+    # 100; dense pass 1 with the frontier bitmaps, the lists without
+    "win_gossip": dict(k=12, topics=1, slots=128, reuse=100, start=25, count=120, tail=28),
+    # four topics: lists, k_push on
+    "win_gossip_4t": dict(k=12, topics=4, slots=128, reuse=100, start=25, count=120, tail=27),
+    # 64 topics x 256 slots: W = 256 words, the layout's maximum; one message
+    # per hop over all topics (a ring of 256 slots does not wrap at that rate)
+    "win_gossip_64t": dict(k=12, topics=64, slots=256, reuse=100, start=25, count=130, shared=True, tail=27),
+    # the adversarial instantiation (an accepting validator, no attackers): the
+    # long window, maxAge (HistoryLength + HistoryGossip + 3) heartbeats
+    "win_adv": dict(k=12, topics=1, validate=True, p3_after=60 * Second, slots=256, reuse=200, start=25,
+                    count=220, tail=128),
+    # win_gossip's network with one disconnect scheduled in the body after the
+    # last publish: the event alone switches the long window on
+    "win_events": dict(k=12, topics=1, event_at=25 + 220 + 2, p3_after=60 * Second, slots=256, reuse=200,
+                       start=25, count=220, tail=128),
+    # parameters that move the formula: HistoryLength 3, HistoryGossip 2, a
+    # 700 ms heartbeat (H = 7): maxAge 21, retireHops 21 + 5 * 7 = 56; the
+    # default IWantFollowupTime (30 hops) is kept
+    "win_gossip_h7": dict(k=12, topics=1, hist=(3, 2, 700 * Millisecond), slots=64, reuse=56, start=22, count=100,
+                          tail=19),
+}
+
+
+def _win(fam, d=0, **over):
+    return lambda lib, x=(): window_run(lib, fam, tail=WINDOW_FAMILIES[fam]["tail"] + d, extra=x, **over)
+
+
+WINDOW_EDGE = {fam + "_edge": _win(fam) for fam in WINDOW_FAMILIES}
+WINDOW_OVER = {fam + "_over": _win(fam, 1) for fam in WINDOW_FAMILIES}
+SCENARIOS.update(WINDOW_EDGE)

@@ -28,7 +28,9 @@ GOLDEN = json.load(open(os.path.join(HERE, "golden", "scenarios.json")))
 DENSE = ["gossipsub_dense", "gossipsub_scored", "gossipsub_flood_publish", "gossipsub_negative_app",
          "gossipsub_dense_dhi", "gossipsub_slot_reuse", "gossipsub_graylist_direct", "c3shape", "floodsub_dense",
          # several topics with partial subscriptions (k_flood_a), and 64-lane rows beside rows of 1 and 0
-         "floodsub_multitopic", "ladder_floodsub_mt", "ladder_scored"]
+         "floodsub_multitopic", "ladder_floodsub_mt", "ladder_scored",
+         # first deliveries of age maxAge, slots used again at retireHops (scenarios.WINDOW_EDGE)
+         "win_flood_edge", "win_flood_3t_edge", "win_gossip_edge", "win_gossip_h7_edge"]
 LISTS_ONLY = ["gossipsub_multitopic", "adversarial_mix", "churn_scored"]
 
 

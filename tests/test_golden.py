@@ -33,7 +33,9 @@ def test_gpu_reproduces_golden(name):
 # phase B (IWANT serving, IHAVE handling, spam, cuts) run three more times.
 RACE_PRONE = ["gossipsub_dense_dhi", "c5shape", "adversarial_mix", "spam_ihave_2t", "churn_graft",
               # full waves: 64 peers per node, 64 topics / 64 senders per validation queue
-              "ladder_64t", "ladder_adversarial"]
+              "ladder_64t", "ladder_adversarial",
+              # a young-slot table with every age 1..maxAge in it at every hop
+              "win_gossip_edge"]
 
 
 @pytest.mark.gpu
@@ -51,7 +53,9 @@ def test_gpu_golden_repeatable(name):
 # a node's own table has room.  The goldens must not move.
 PEERTX_SPILL = ["c3shape", "adversarial_mix", "gossipsub_slot_reuse", "churn_scored", "c4shape", "px_adversarial",
                 # a host serving 64 peers from 4 slots spills at once
-                "ladder_scored"]
+                "ladder_scored",
+                # peertx entries of slots that are used again at retireHops
+                "win_gossip_edge", "win_adv_edge"]
 
 
 @pytest.mark.gpu

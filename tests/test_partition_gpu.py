@@ -157,6 +157,10 @@ def run_partitioned(world, name, oracle):
     (2, "ladder_randomsub_100"),
     (3, "ladder_4t_flood"),
     (2, "ladder_adversarial"),
+    # the message-window edge: the tail (the last rank's) takes every message
+    # at age maxAge, slots are used again at retireHops
+    (2, "win_gossip_edge"),
+    (3, "win_flood_edge"),
 ])
 def test_partitioned_engine_matches_oracle(world, name, oracle_path):
     res = run_partitioned(world, name, oracle_path)

@@ -27,6 +27,9 @@ T = _abi.TRACE_TYPES.index
 def traced_nodes(name):
     if name.startswith("ladder_"):
         return LADDER_TRACED
+    if name.startswith("win_"):  # the tail's tip, its neighbour and the node the tail hangs on
+        n = scenarios.WIN_BODY + scenarios.WINDOW_FAMILIES[name.rsplit("_", 1)[0]]["tail"]
+        return [0, n - 2, n - 1]
     return [u for u in TRACED if u < 20] if name == "floodsub_dense" else [u for u in TRACED if u < 120]
 
 
@@ -41,7 +44,7 @@ def traced_run(lib, name, nodes=TRACED, extra=()):
     return e, np.concatenate(evs)
 
 
-def check_invariants(e, ev, nodes):
+def check_invariants(e, ev, nodes, prunes=True):
     assert len(ev)
     key = [(r["hop"], r["node"], r["phase"]) for r in ev]
     assert key == sorted(key), "events out of canonical order"
@@ -49,7 +52,7 @@ def check_invariants(e, ev, nodes):
     want = {T("ADD_PEER"), T("JOIN"), T("PUBLISH_MESSAGE"), T("DELIVER_MESSAGE"), T("DUPLICATE_MESSAGE")}
     if e.router == _abi.GS_ROUTER_GOSSIPSUB:
         # a mixed network's few traced gossipsub hosts may never prune
-        want |= {T("GRAFT")} if getattr(e, "routers", None) is not None else {T("GRAFT"), T("PRUNE")}
+        want |= {T("GRAFT")} if getattr(e, "routers", None) is not None or not prunes else {T("GRAFT"), T("PRUNE")}
     assert want <= types, f"missing event types {want - types}"
     deg = np.diff(e.rowptr)
     mesh = e.mesh()
@@ -237,6 +240,35 @@ def test_gpu_trace_equals_oracle(oracle_path, name):
     bad = np.nonzero(got != ref)[0]
     assert len(bad) == 0, f"{len(bad)} events differ, first {got[bad[0]]} vs {ref[bad[0]]}"
     check_invariants(e, got, nodes)
+
+
+def _window_edge_trace(oracle_path):
+    """win_gossip_edge's oracle stream of the tail's tip, its neighbour and
+    node 0, its invariants checked on the oracle's engine (which reads back
+    every message; the GPU engine's slots are used again during the run; no
+    host has more than Dhi mesh candidates, so nobody prunes), with a
+    DeliverMessage of age maxAge at the tip."""
+    from test_window import family_window
+    name = "win_gossip_edge"
+    nodes = traced_nodes(name)
+    eo, ref = traced_run(oracle_path, name, nodes)
+    check_invariants(eo, ref, nodes, prunes=False)
+    dl = ref[(ref["type"] == T("DELIVER_MESSAGE")) & (ref["node"] == nodes[-1])]
+    assert (dl["hop"] - eo.sched_hops[dl["msg"]]).max() == family_window("win_gossip")[0]
+    return nodes, ref
+
+
+def test_oracle_trace_at_the_window_edge(oracle_path):
+    _window_edge_trace(oracle_path)
+
+
+@pytest.mark.gpu
+def test_gpu_trace_equals_oracle_at_the_window_edge(oracle_path):
+    nodes, ref = _window_edge_trace(oracle_path)
+    _, got = traced_run(PRODUCT_LIB, "win_gossip_edge", nodes)
+    assert len(got) == len(ref), (len(got), len(ref))
+    bad = np.nonzero(got != ref)[0]
+    assert len(bad) == 0, f"{len(bad)} events differ, first {got[bad[0]]} vs {ref[bad[0]]}"
 
 
 @pytest.mark.gpu
