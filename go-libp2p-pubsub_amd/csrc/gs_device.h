@@ -689,6 +689,13 @@ __device__ __forceinline__ double eff_mmd(const TopicP& tp, double mmd, uint32_t
 
 // One topic's contribution topicScore * TopicWeight (score.go:265-311) of
 // pair i, split into its loads (all issued at once) and its arithmetic.
+// flags[i] of a pair: bit 0 = in the mesh, bit 1 = P3 active, and GS_FL_MFP =
+// mfp[i] may be non-zero.  Invariant: bit clear => mfp[i] == 0, so the
+// streaming refresh skips the mfp read of (nearly) every pair; set wherever a
+// penalty is added, kept by a graft, cleared once the refresh decays it to 0
+// and where the record is zeroed.  Readers that export flags mask to GS_FL_PUB.
+#define GS_FL_MFP 4
+#define GS_FL_PUB 3
 struct TermIn {
   double fmd, mm, mfp, im;
   int64_t mt;
@@ -844,7 +851,7 @@ __device__ __forceinline__ void stats_graft(const Dev& d, int64_t e, int t, int6
   if (!d.scoring || !d.tp[t].scored) return;
   const int64_t i = tix(d, t, e);
   d.sdirty[e] = 1;
-  d.flags[i] = 1;  // inMesh, P3 inactive
+  d.flags[i] = (d.flags[i] & GS_FL_MFP) | 1;  // inMesh, P3 inactive; a penalty from an earlier prune stays marked
   d.graftTime[i] = now;
   d.meshTime[i] = 0;
 }
@@ -864,12 +871,14 @@ __device__ __forceinline__ void stats_prune(const Dev& d, int64_t e, int t) {
     dlt_put(d, i, q & 0xFFFF);
   }
   const double thr = tp.MmdThreshold;
+  uint8_t nfl = fl & ~1;
   if ((fl & 2) && mm < thr) {
     const double deficit = thr - mm;
     d.mfp[i] += deficit * deficit;
+    nfl |= GS_FL_MFP;
   }
   if (fl & 1) d.meshTime[i] = mesh_time_of(d.lastRefresh, d.graftTime[i]);  // kept as it was at the prune
-  d.flags[i] = fl & ~1;
+  d.flags[i] = nfl;
 }
 
 // doAddBackoff — gossipsub.go:844-854 (0 = no entry)

@@ -1173,7 +1173,7 @@ int gs_engine::phaseB(const Hop& hp) {
 // delivery counts.
 void gs_engine::refreshOrFold(const Hop& hp) {
   if (refreshDue(hp.now)) {
-    const unsigned rb = nblk(eOwn, GS_RP / T);
+    const unsigned rb = nblk(eOwn, GS_RG * (GS_RP / T));  // a wave per GS_RG groups of GS_RP / T edges
     const bool laneT = (64 % T) == 0;  // a lane keeps one topic; narrowDlt: St <= 254 and T even
     TIMED(this, GS_K_REFRESH, with_consts([&](auto ndltC, auto churnC, auto laneC) {
             k_refresh_rows<CV(churnC), CV(laneC), CV(ndltC)><<<rb, 64, 0, stream>>>(d, hp.now);
@@ -2199,8 +2199,10 @@ int gs_read_topic_stats(gs_engine* g, double* fmd, double* mmd, double* mfp, dou
   GS_TRY(copy_back_pairs(g, flags, (const uint8_t*)g->d.flags));
   // a mesh pair's meshTime is derived (mesh_time_of, gs_device.h)
   const int64_t lr = g->d.lastRefresh;
-  for (int64_t i = 0; i < (int64_t)g->E * g->T; ++i)
+  for (int64_t i = 0; i < (int64_t)g->E * g->T; ++i) {
     if (flags[i] & 1) mesh_time[i] = graft_time[i] <= lr ? lr - graft_time[i] : 0;
+    flags[i] &= GS_FL_PUB;  // (GS_FL_MFP is the engine's own)
+  }
   return GS_OK;
 }
 int gs_read_behaviour_penalty(gs_engine* g, double* bp) { return copy_back_edges(g, bp, g->d.bp); }

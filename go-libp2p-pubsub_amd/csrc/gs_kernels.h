@@ -2,7 +2,7 @@
 //
 // Kernel map (one hop):
 //   k_score_rows   wave/64 edges peerScore.score (+ memos)  score.go:256-333
-//   k_refresh_rows wave/1024 pairs refreshScores (+ exact S0) score.go:495-556
+//   k_refresh_rows wave/8 x 1024 pairs refreshScores (+ exact S0) score.go:495-556
 //   k_join         wave/node     Join at hop 0              gossipsub.go:1011-1060
 //   k_fanout_pub   wave/pair     Publish fanout creation    gossipsub.go:977-994
 //   k_fwd          thread/edge   forwarding-target snapshot gossipsub.go:953-999, floodsub.go:85, randomsub.go:115
@@ -50,7 +50,7 @@
 //     the few scores it needs as values (Dhi ranking) from the same rule.
 #define GS_SB 8   // passes per load batch
 #ifndef GS_RB
-#define GS_RB 8   // refresh: pairs per lane per load batch
+#define GS_RB 4   // refresh: pairs per lane in flight (the ring's register sets)
 #endif
 #define GS_RP 1024  // (edge, topic) pairs of one wave's LDS term table
 __device__ __forceinline__ int rp_pad(int pl) { return pl + (pl >> 6); }
@@ -109,7 +109,10 @@ __global__ __launch_bounds__(64) void k_score_rows(Dev d, double* __restrict__ o
   const int gi = LANE_T ? lane / T : 0;
   const int tl = LANE_T ? (lane & (T - 1)) : (lane < T ? lane : 0);
   const bool lt = LANE_T || lane < T;
-  const bool scoredL = lt && d.tp[tl].scored;
+  // the lane's topic params by value: read through d.tp inside the loop they
+  // would be loaded again after every store of the sums below
+  const TopicP tpL = d.tp[tl];
+  const bool scoredL = lt && tpL.scored;
   const uint64_t scoredT = __ballot(lane < T && d.tp[lane < T ? lane : 0].scored);
   for (int c0 = 0; c0 < nNeed; c0 += sgw) {
     const int nc = min(sgw, nNeed - c0);  // the chunk's edges: positions 0 .. nc - 1
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(64) void k_score_rows(Dev d, double* __restrict__ o
         x[k] = term_load(d, (eb + sList[c0 + (js[k] < 0 ? 0 : js[k])]) * T + tl);
 #pragma unroll
       for (int k = 0; k < GS_SB; ++k)
-        if (js[k] >= 0) sT[rp_pad(js[k] * T + tl)] = scoredL ? term_eval(d.tp[tl], x[k]) : 0.0;
+        if (js[k] >= 0) sT[rp_pad(js[k] * T + tl)] = scoredL ? term_eval(tpL, x[k]) : 0.0;
     }
     __syncthreads();
     for (int j = lane; j < nc; j += 64) {
@@ -149,144 +152,256 @@ __global__ __launch_bounds__(64) void k_score_rows(Dev d, double* __restrict__ o
 // the refreshed state into S0 (sdirty cleared): nothing but refreshScores
 // changed the state since the hop's message phase, so this is the value the
 // next S0 pass would compute.
-// A wave owns GS_RP consecutive (edge, topic) pairs — GS_RP / T whole edges —
-// and lane l takes pairs l, l + 64, ...: every lane busy for any T (at T = 1
-// a wave covers 1024 edges, at T = 64 sixteen, one topic per lane).  LANE_T:
-// T divides 64, so a lane's topic is fixed (lane % T) and its params stay in
-// registers; otherwise each pair finds its own.  Terms go to LDS (one pad
-// word per 64: conflict-free at T = 64) and the sum per edge runs in
-// ascending topic order, as the reference's loop does.
+// A group is GS_RP consecutive (edge, topic) pairs — GS_RP / T whole edges,
+// the LDS term table's — in GS_RS slots of 64: lane l takes pairs l, l + 64,
+// ..., so every lane is busy for any T (at T = 1 a group covers 1024 edges, at
+// T = 64 sixteen, one topic per lane).  Terms go to LDS (one pad word per 64:
+// conflict-free at T = 64) and the sum per edge runs in ascending topic
+// order, as the reference's loop does.
+// A wave owns GS_RG consecutive groups and streams their slots through a ring
+// of GS_RB register sets: slot s is processed and its set refilled at once
+// with slot s + GS_RB, across group boundaries, so the loads never drain — a
+// group's serial sum and tail run with the next group's first slots in
+// flight — and every wait counts down to the one slot it needs.
+// The topic params must not be read through d.tp inside the loop: the kernel's
+// own stores may alias that table, so every field would be loaded again after
+// every store (17 extra vector loads per pair, each under a full wait).
+// LANE_T: T divides 64, so a lane's topic is fixed (lane % T) and a by-value
+// copy of its params stays in registers; otherwise (or with GS_RF_TPLDS) they
+// come from a field-major LDS copy of the table, indexed by the pair's topic.
+// mfp is read only where flag bit 2 says it may be non-zero (GS_FL_MFP: a few
+// hundred pairs of 2e9 at config4), by a wave-uniform branch.
 // CHURN: some connection may be down (gs_schedule_events): retained records
 // are not decayed and expire; the honest instantiation carries none of it.
+#ifndef GS_RG
+#define GS_RG 8  // refresh: groups per wave
+#endif
+#ifndef GS_RF_TPLDS
+#define GS_RF_TPLDS 0  // timing A/B: 1 keeps the topic params in LDS for every T
+#endif
+#ifndef GS_RF_MFPBIT
+#define GS_RF_MFPBIT 1  // timing A/B: 0 streams mfp with the other arrays
+#endif
+#define GS_RS (GS_RP / 64)  // slots of a group
+constexpr int GS_TPW = (int)(sizeof(TopicP) / 8);
+static_assert(sizeof(TopicP) % 8 == 0, "TopicP is copied to LDS in 64-bit words");
+__device__ __forceinline__ TopicP tp_from_lds(const uint64_t (*s)[64], int t) {
+  uint64_t w[GS_TPW];
+#pragma unroll
+  for (int f = 0; f < GS_TPW; ++f) w[f] = s[f][t];  // (only the fields the caller uses are read)
+  TopicP p;
+  __builtin_memcpy(&p, w, sizeof(TopicP));
+  return p;
+}
+// base[c] of a wave-uniform base: the 32-bit byte offset keeps the address a
+// scalar base plus one offset register per lane (no 64-bit address pair per
+// array and slot)
+template <class X>
+__device__ __forceinline__ X& at_u(X* base, unsigned c) {
+  return *(X*)((char*)base + (size_t)(c * (unsigned)sizeof(X)));
+}
+struct RfIn {  // one pair's state as loaded
+  double fmd, mmd, mfp, imd;
+  int64_t gt;
+  uint32_t q;    // wide pending counts
+  uint16_t qn;   // narrow ones, packed as stored
+  uint8_t fl;
+};
 template <bool CHURN, bool LANE_T, bool NDLT>
 __global__ __launch_bounds__(64) GS_OCC_RF void k_refresh_rows(Dev d, int64_t now) {
+  static_assert(GS_RS % GS_RB == 0, "a ring turn stays within one group");
+  constexpr bool TP_REG = LANE_T && !GS_RF_TPLDS;
+  constexpr bool MFPBIT = GS_RF_MFPBIT != 0;
   __shared__ double sT[GS_RP + GS_RP / 64];
+  __shared__ uint64_t sTp[TP_REG ? 1 : GS_TPW][64];  // [field][topic]: conflict-free 64-bit reads
   const int lane = lane_id();
   const int T = d.T;
-  const int epw = GS_RP / T;
-  const int64_t e0 = d.e0 + (int64_t)blockIdx.x * epw;
-  const int ng = (int)min((int64_t)epw, d.e1 - e0);
-  const int np = ng * T;
-  const int64_t p0 = e0 * T;
+  const int epw = GS_RP / T;     // edges of a group
+  const int gPairs = epw * T;    // pairs of a full group
+  const int64_t eW = d.e0 + (int64_t)blockIdx.x * (GS_RG * epw);
+  if (eW >= d.e1) return;
+  const int64_t eEnd = min(d.e1, eW + (int64_t)GS_RG * epw);
+  const int nGrp = (int)((eEnd - eW + epw - 1) / epw);
+  const int64_t pW = eW * T, pEnd = eEnd * T;
   const int tl = lane < T ? lane : 0;
   const uint64_t scoredT = __ballot(lane < T && d.tp[tl].scored);
   const int tLane = LANE_T ? (lane & (T - 1)) : 0;
+  TopicP tpR{};
+  if constexpr (TP_REG) {
+    tpR = d.tp[tLane];
+  } else {
+    if (lane < T) {
+      const TopicP g = d.tp[lane];
+      uint64_t w[GS_TPW];
+      __builtin_memcpy(w, &g, sizeof(TopicP));
+#pragma unroll
+      for (int f = 0; f < GS_TPW; ++f) sTp[f][lane] = w[f];
+    }
+    __syncthreads();
+  }
+  // the 64 pairs from pB + rel: pB is a group's first pair (wave-uniform, so
+  // every array's address is a scalar base plus a 32-bit lane offset — no
+  // 64-bit address registers per array); past the wave's last pair the loads
+  // repeat it (never used)
+  auto load = [&](int64_t pB, int rel) -> RfIn {
+    const unsigned c = (unsigned)min(rel + lane, (int)(pEnd - 1 - pB));
+    RfIn x;
+    // (the narrow counts stay as loaded until their slot's turn: widened or
+    // unpacked here, behind the load, they would be waited for at once)
+    x.q = 0;
+    x.qn = 0;
+    if constexpr (NDLT) x.qn = at_u(d.dltN + pB, c);
+    else x.q = at_u(d.dlt + pB, c);
+    x.fmd = at_u(d.fmd + pB, c);
+    x.mmd = at_u(d.mmd + pB, c);
+    x.mfp = MFPBIT ? 0.0 : at_u(d.mfp + pB, c);
+    x.imd = d.anyImd ? at_u(d.imd + pB, c) : 0.0;
+    x.gt = at_u(d.graftTime + pB, c);
+    x.fl = at_u(d.flags + pB, c);
+    return x;
+  };
   // the score tail's per-edge inputs (P5 app score through col, P6, P7) of the
-  // lane's edge, loaded with the first batch instead of after the topic sums
-  // (one edge per lane when the wave covers at most 64 edges)
-  double tApp = 0.0, tP6 = 0.0, tBp = 0.0;
-  if (epw <= 64 && lane < ng) {
-    const int64_t e = e0 + lane;
-    tApp = d.app[d.col[e]];
-    tP6 = d.p6[e];
-    tBp = d.bp[e];
-  }
-  for (int k0 = 0; 64 * k0 < np; k0 += GS_RB) {
-    uint32_t q[GS_RB];
-    double fmd[GS_RB], mmd[GS_RB], mfp[GS_RB], imd[GS_RB];
-    int64_t gt[GS_RB];
-    uint8_t fl[GS_RB];
+  // lane's edge (one edge per lane when a group covers at most 64 edges) are
+  // fetched a group ahead: col before a group's ring turns, and p6, bp and
+  // app[col] after its sum — col has long arrived by then, so the wait for it
+  // leaves the ring in flight, and the sum has read the current values, so
+  // the new ones load into the same registers (a copy would wait for them).
+  // Unconditional (clamped to the wave's last edge), so no value is merged or
+  // copied under a wait either; without `pre` they are simply not used.
+  const bool pre = epw <= 64;
+  const int64_t eL = min(eW + lane, eEnd - 1);
+  double tP6 = d.p6[eL], tBp = d.bp[eL], tApp = d.app[d.col[eL]];
+  RfIn in[GS_RB];
 #pragma unroll
-    for (int k = 0; k < GS_RB; ++k) {
-      const int pl = min(lane + 64 * (k0 + k), np - 1);
-      const int64_t i = p0 + pl;
-      q[k] = dlt_get_t<NDLT>(d, i);
-      fmd[k] = d.fmd[i];
-      mmd[k] = d.mmd[i];
-      mfp[k] = d.mfp[i];
-      imd[k] = d.anyImd ? d.imd[i] : 0.0;
-      gt[k] = d.graftTime[i];
-      fl[k] = d.flags[i];
-    }
+  for (int k = 0; k < GS_RB; ++k) in[k] = load(pW, 64 * k);
+  for (int g = 0; g < nGrp; ++g) {
+    const int64_t e0 = eW + (int64_t)g * epw;
+    const int ng = (int)min((int64_t)epw, eEnd - e0);
+    const int np = ng * T;
+    const int64_t p0 = e0 * T;
+    const int64_t eN = min(e0 + epw + lane, eEnd - 1);  // the lane's edge of the next group
+    const uint32_t nCol = (uint32_t)d.col[eN];  // (unsigned: no sign extension right behind the load)
+#pragma unroll 1
+    for (int sb = 0; sb < GS_RS; sb += GS_RB) {
+      const bool lastTurn = sb == GS_RS - GS_RB;
+      // the refill: slot sb + k + GS_RB of this group, or (last turn) slot k of
+      // the next, whose first pair is p0 + gPairs
+      const int relNext = lastTurn ? gPairs : 64 * (sb + GS_RB);
 #pragma unroll
-    for (int k = 0; k < GS_RB; ++k) {
-      const int pl = lane + 64 * (k0 + k);
-      if (pl >= np) break;
-      const int64_t i = p0 + pl;
-      int t = tLane;
-      int64_t e = 0;
-      if (!LANE_T || CHURN) {
-        pair_split(d, i, e, t);
-        if (LANE_T) t = tLane;
-      }
-      const TopicP& tp = d.tp[t];
-      const bool act = (scoredT >> t) & 1;
-      double term = 0.0;
-      uint8_t st = 1;
-      if (CHURN && d.rstate != nullptr) st = d.rstate[e];
-      if (CHURN && st != 1) {
-        // a retained record is not decayed; past its expiry it is dropped
-        // (score.go:500-509); the host then recounts P6 (removeIPs)
-        if (st == 2 && now > d.rexpire[e]) {
-          d.fmd[i] = 0; d.mmd[i] = 0; d.mfp[i] = 0; d.imd[i] = 0; dlt_put_t<NDLT>(d, i, 0);
-          d.meshTime[i] = 0; d.graftTime[i] = 0; d.flags[i] = 0;
-        } else if (act) {
-          term = topic_term(d, tp, i);  // the stored record as it is
-        }
-      } else if (act) {
-        TermIn x;
-        x.q = 0;
-        double v = eff_fmd(tp, fmd[k], q[k]) * tp.FmdDecay;
-        if (v < d.DecayToZero) v = 0;
-        x.fmd = v;
-        v = eff_mmd(tp, mmd[k], q[k]) * tp.MmdDecay;
-        if (v < d.DecayToZero) v = 0;
-        x.mm = v;
-        v = mfp[k] * tp.MfpDecay;
-        if (v < d.DecayToZero) v = 0;
-        x.mfp = v;
-        v = imd[k] * tp.ImdDecay;
-        if (v < d.DecayToZero) v = 0;
-        x.im = v;
-        x.fl = fl[k];
-        x.mt = 0;
-        // unchanged counters (mostly zeros staying zero) are not written back
-        if (q[k]) dlt_put_t<NDLT>(d, i, 0);
-        if (x.fmd != fmd[k]) d.fmd[i] = x.fmd;
-        if (x.mm != mmd[k]) d.mmd[i] = x.mm;
-        if (x.mfp != mfp[k]) d.mfp[i] = x.mfp;
-        if (d.anyImd && x.im != imd[k]) d.imd[i] = x.im;
-        if (x.fl & 1) {
-          x.mt = now - gt[k];  // meshTime (score.go:518-520): mesh_time_of() from here on
-          if (x.mt > tp.MmdActivation) {
-            x.fl |= 2;
-            d.flags[i] = x.fl;
+      for (int k = 0; k < GS_RB; ++k) {
+        const int pl = 64 * (sb + k) + lane;
+        const unsigned ul = (unsigned)pl;
+        RfIn r = in[k];
+        if constexpr (NDLT) r.q = (r.qn & 0xFFu) | ((uint32_t)(r.qn >> 8) << 16);
+        if (pl < np) {
+          const int64_t i = p0 + pl;
+          int t = tLane;
+          int64_t e = 0;
+          if (!LANE_T || CHURN) {
+            pair_split(d, i, e, t);
+            if (LANE_T) t = tLane;
           }
+          if constexpr (LANE_T && !TP_REG) asm volatile("" : "+v"(t));  // (keeps the A/B's reads in LDS)
+          const TopicP tp = TP_REG ? tpR : tp_from_lds(sTp, t);
+          const bool act = (scoredT >> t) & 1;
+          double term = 0.0;
+          uint8_t st = 1;
+          if (CHURN && d.rstate != nullptr) st = d.rstate[e];
+          if (CHURN && st != 1) {
+            // a retained record is not decayed; past its expiry it is dropped
+            // (score.go:500-509); the host then recounts P6 (removeIPs)
+            if (st == 2 && now > d.rexpire[e]) {
+              d.fmd[i] = 0; d.mmd[i] = 0; d.mfp[i] = 0; d.imd[i] = 0; dlt_put_t<NDLT>(d, i, 0);
+              d.meshTime[i] = 0; d.graftTime[i] = 0; d.flags[i] = 0;
+            } else if (act) {
+              term = topic_term(d, tp, i);  // the stored record as it is
+            }
+          } else if (act) {
+            TermIn x;
+            x.q = 0;
+            double v = eff_fmd(tp, r.fmd, r.q) * tp.FmdDecay;
+            if (v < d.DecayToZero) v = 0;
+            x.fmd = v;
+            v = eff_mmd(tp, r.mmd, r.q) * tp.MmdDecay;
+            if (v < d.DecayToZero) v = 0;
+            x.mm = v;
+            x.fl = r.fl;
+            x.mfp = 0.0;
+            if (!MFPBIT || (r.fl & GS_FL_MFP)) {
+              // (MFPBIT: rare, so the branch is skipped by nearly every wave;
+              // the load and its wait stay inside it)
+              const double m = MFPBIT ? at_u(d.mfp + p0, ul) : r.mfp;
+              v = m * tp.MfpDecay;
+              if (v < d.DecayToZero) v = 0;
+              if (v != m) at_u(d.mfp + p0, ul) = v;
+              if (v == 0) x.fl &= ~GS_FL_MFP;  // decayed to zero: the next refresh skips it
+              x.mfp = v;
+            }
+            v = r.imd * tp.ImdDecay;
+            if (v < d.DecayToZero) v = 0;
+            x.im = v;
+            x.mt = 0;
+            // unchanged counters (mostly zeros staying zero) are not written back
+            if (r.q) {
+              if constexpr (NDLT) at_u(d.dltN + p0, ul) = 0;
+              else at_u(d.dlt + p0, ul) = 0;
+            }
+            if (x.fmd != r.fmd) at_u(d.fmd + p0, ul) = x.fmd;
+            if (x.mm != r.mmd) at_u(d.mmd + p0, ul) = x.mm;
+            if (d.anyImd && x.im != r.imd) at_u(d.imd + p0, ul) = x.im;
+            if (x.fl & 1) {
+              x.mt = now - r.gt;  // meshTime (score.go:518-520): mesh_time_of() from here on
+              if (x.mt > tp.MmdActivation) x.fl |= 2;
+            }
+            if (x.fl != r.fl) at_u(d.flags + p0, ul) = x.fl;
+            term = term_eval(tp, x);
+          }
+          sT[rp_pad(pl)] = term;
         }
-        term = term_eval(tp, x);
+        in[k] = load(p0, relNext + 64 * k);
       }
-      sT[rp_pad(pl)] = term;
     }
-  }
-  __syncthreads();
-  for (int j = lane; j < ng; j += 64) {
-    const int64_t e = e0 + j;
-    bool frozen = false, dropped = false;
-    if (CHURN && d.rstate != nullptr) {
-      const uint8_t st = d.rstate[e];
-      frozen = st != 1;
-      dropped = st == 2 && now > d.rexpire[e];
+    __syncthreads();
+    // (one copy of the loop per `pre`: where the two share code, the waits of
+    // the loads that only !pre issues would drain the ring for both)
+    auto sums = [&](auto preC) {
+    constexpr bool pre = decltype(preC)::value;
+    for (int j = lane; j < ng; j += 64) {
+      const int64_t e = e0 + j;
+      bool frozen = false, dropped = false;
+      if (CHURN && d.rstate != nullptr) {
+        const uint8_t st = d.rstate[e];
+        frozen = st != 1;
+        dropped = st == 2 && now > d.rexpire[e];
+      }
+      // pre: tail inputs already in registers (lane j == edge j)
+      double b = pre ? tBp : d.bp[e];
+      if (dropped) {
+        b = 0;
+        d.bp[e] = 0;
+        d.rstate[e] = 0;
+      } else if (!frozen) {
+        b *= d.BPDecay;
+        if (b < d.DecayToZero) b = 0;
+        d.bp[e] = b;
+      }
+      double score = 0.0;
+      if (d.scoring && !dropped && (!CHURN || has_record(d, e))) {
+        for (int t = 0; t < T; ++t)
+          if ((scoredT >> t) & 1) score += sT[rp_pad(j * T + t)];
+        // score_tail with the refreshed P7 (d.bp[e] == b after the store above)
+        score = pre ? score_tail_v(d, score, tApp, tP6, b) : score_tail(d, e, score);
+      }
+      d.score0[e] = score;
+      d.sdirty[e] = 0;
     }
-    const bool pre = epw <= 64;  // tail inputs already in registers (lane j == edge j)
-    double b = pre ? tBp : d.bp[e];
-    if (dropped) {
-      b = 0;
-      d.bp[e] = 0;
-      d.rstate[e] = 0;
-    } else if (!frozen) {
-      b *= d.BPDecay;
-      if (b < d.DecayToZero) b = 0;
-      d.bp[e] = b;
-    }
-    double score = 0.0;
-    if (d.scoring && !dropped && (!CHURN || has_record(d, e))) {
-      for (int t = 0; t < T; ++t)
-        if ((scoredT >> t) & 1) score += sT[rp_pad(j * T + t)];
-      // score_tail with the refreshed P7 (d.bp[e] == b after the store above)
-      score = pre ? score_tail_v(d, score, tApp, tP6, b) : score_tail(d, e, score);
-    }
-    d.score0[e] = score;
-    d.sdirty[e] = 0;
+    };
+    if (pre) sums(std::true_type{});
+    else sums(std::false_type{});
+    __syncthreads();  // the term table is the next group's
+    tP6 = d.p6[eN];
+    tBp = d.bp[eN];
+    tApp = d.app[nCol];
   }
 }
 
@@ -331,7 +446,7 @@ __global__ void k_gather_pairs(Dev d, const int64_t* __restrict__ edges, int64_t
   o[3 * nk + k] = d.imd[i];
   oi[4 * nk + k] = (d.flags[i] & 1) ? mesh_time_of(d.lastRefresh, d.graftTime[i]) : d.meshTime[i];
   oi[5 * nk + k] = d.graftTime[i];
-  of[k] = d.flags[i];
+  of[k] = d.flags[i] & GS_FL_PUB;
 }
 
 // gs_read_backoff_edges: the backoff expiries of n chosen edges, out[i*T + t]

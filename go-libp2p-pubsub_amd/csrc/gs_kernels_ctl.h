@@ -2377,12 +2377,14 @@ __global__ __launch_bounds__(64) void k_edge_down(Dev d, const int32_t* __restri
     d.fmd[i] = 0;
     dlt_put(d, i, 0);
     const uint8_t fl = d.flags[i];
+    uint8_t nfl = fl & ~1;
     if ((fl & 1) && (fl & 2) && mm < tp.MmdThreshold) {
       const double deficit = tp.MmdThreshold - mm;
       d.mfp[i] += deficit * deficit;
+      nfl |= GS_FL_MFP;
     }
     if (fl & 1) d.meshTime[i] = mesh_time_of(d.lastRefresh, d.graftTime[i]);  // the retained record's
-    d.flags[i] = fl & ~1;
+    d.flags[i] = nfl;
   }
   if (lane == 0) {
     if (drop) {
