@@ -276,7 +276,7 @@ struct Dev {
   uint8_t* jrIn;  // [E] position of the receiver in the sender's row: rev[e] - rowptr[col[e]]
   double* score0;  // hop-start score memo (S0)
   double* score1;  // after the message phase (S1) / heartbeat memo
-  uint8_t* sdirty; // [E] a score-lowering change (graft/prune/penalty/refresh) since score0
+  uint8_t* sdirty; // [E] a score-lowering change (graft/prune/penalty/refresh/P6 recount) since score0
   int64_t* backoff;  // [T][E], 0 = none
   uint64_t* boMask;  // [E] bit t: backoff of (e, t) is set (the heartbeat's candidate filter
                      // reads one coalesced word per edge instead of a strided expiry per topic)

@@ -33,9 +33,12 @@
 //     thresholds <= PublishThreshold (AcceptFrom graylist, publish / fanout
 //     filters; thresholds are <= 0 by validation, score_params.go:34-51), and
 //     between two recomputations the score can only rise unless a graft,
-//     prune, penalty or refresh touched the edge (message deliveries raise P2
-//     and lower the P3 deficit; FirstMessageDeliveriesWeight >= 0 and
-//     MeshMessageDeliveriesWeight <= 0 by validation).  So a memo that is
+//     prune, penalty, refresh or P6 recount touched the edge (message
+//     deliveries raise P2 and lower the P3 deficit; FirstMessageDeliveriesWeight
+//     >= 0 and MeshMessageDeliveriesWeight <= 0 by validation; k_p6 marks the
+//     edges whose colocation factor it changed: the other peers on the IP of
+//     a connection that came up or went down, or of an expired record, which
+//     k_edge_up / k_edge_down / the refresh do not touch).  So a memo that is
 //     >= PublishThreshold and not dirty gives the same decisions as the exact
 //     score; everything else is recomputed exactly.
 //   MODE 2: memo S1 for HandleRPC (after the message phase): its decisions

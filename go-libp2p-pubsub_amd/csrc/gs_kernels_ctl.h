@@ -2414,7 +2414,12 @@ __global__ void k_edge_up(Dev d, const int32_t* __restrict__ edges, int n, int64
 
 // ipColocationFactor (score.go:335-379) after the record set changed: per
 // observer (one wave per node, lane = edge) the peers with a record that share
-// the edge's IP.
+// the edge's IP.  A recount moves the scores of the other peers on the IP of
+// the connection that changed, down as well as up, and nothing else touches
+// those edges: where the factor of an edge with a record changes, the edge is
+// marked dirty, so the score memos (k_score_rows) are recomputed for it — by
+// the hop's S0 pass after an event, by the heartbeat's pass over the dirty
+// edges (or the next hop's S0 pass) after a refresh that expired records.
 __global__ __launch_bounds__(64) void k_p6(Dev d, double* __restrict__ p6) {
   const int v = d.n0 + blockIdx.x;
   const int lane = lane_id();
@@ -2436,7 +2441,10 @@ __global__ __launch_bounds__(64) void k_p6(Dev d, double* __restrict__ p6) {
     const double s = (double)(cnt - d.IPThr);
     f = s * s;
   }
-  p6[e] = f;
+  if (p6[e] != f) {
+    p6[e] = f;
+    if (has_record(d, e)) d.sdirty[e] = 1;
+  }
 }
 
 // Leave(topic) at node v (handleRemoveSubscription pubsub.go:665-686 ->

@@ -154,6 +154,13 @@ def WithProtocols(proto):
     return ("protocols", np.ascontiguousarray(proto, dtype=np.uint8))
 
 
+def WithIPWhitelist(nets):
+    """PeerScoreParams.IPColocationFactorWhitelist (score_params.go:75, score.go:
+    344-361) as (net, mask) pairs of uint32 (gs_set_ip_whitelist): a peer whose
+    IPv4 address lies in one of the subnets takes no P6 penalty."""
+    return ("ip_whitelist", [(int(n) & 0xFFFFFFFF, int(m) & 0xFFFFFFFF) for n, m in nets])
+
+
 def WithPeertxCapacity(home_bits, overflow_bits):
     """mcache.peertx capacity (gs_set_peertx_capacity): 2^home_bits slots per
     node, and a per-rank overflow table of 2^overflow_bits entries for nodes
@@ -300,6 +307,11 @@ class Engine:
         self.app_attr, self.ipv4_attr = app, ips  # gs_set_peer_attrs inputs (None: zeros)
         if app is not None or ips is not None:
             _check(self.lib, self.lib.gs_set_peer_attrs(h, _ptr(app, C.c_double), _ptr(ips, C.c_uint32)))
+        wl = opts.get("ip_whitelist")
+        if wl is not None:
+            net = np.array([n for n, _ in wl], dtype=np.uint32)
+            mask = np.array([m for _, m in wl], dtype=np.uint32)
+            _check(self.lib, self.lib.gs_set_ip_whitelist(h, len(wl), _ptr(net, C.c_uint32), _ptr(mask, C.c_uint32)))
 
     def close(self):
         if getattr(self, "h", None):

@@ -5,7 +5,7 @@ bit-exactly (float64 compared on their bit patterns)."""
 import numpy as np
 
 from pubsub_amd import (NewFloodSub, NewGossipSub, NewRandomSub, PeerScoreParams, Second,
-                        TopicScoreParams, WithDirectPeers, WithFloodPublish, WithGossipSubParams, WithHop,
+                        TopicScoreParams, WithDirectPeers, WithFloodPublish, WithGossipSubParams, WithHop, WithIPWhitelist,
                         WithMessageWindow, WithPeerScore, WithRecordDeliveries, WithSeed,
                         eth2_peer_score_params, eth2_thresholds, eth2_topic_score_params)
 from pubsub_amd import graphs
@@ -94,8 +94,11 @@ def gossipsub_dense(lib, seed=1, msgs=100, extra=()):
 
 def gossipsub_scored(lib, n=300, k=20, topics=1, seed=3, msgs=300, hb=12, flood=False, sub_frac=1.0,
                      app_neg_frac=0.0, ip_groups=0, params=None, window=1024, extra=(), app_neg=-150.0,
-                     direct_frac=0.0, topic0_frac=0.0, burst=None, graph=None, authors=()):
+                     direct_frac=0.0, topic0_frac=0.0, burst=None, graph=None, authors=(), ip_threshold=None,
+                     ip_weight=None, whitelist=None):
     """gossipsub v1.1 with Eth2-derived scoring over a random regular graph.
+    ip_threshold / ip_weight: P6's IPColocationFactorThreshold / -Weight instead
+    of Eth2's 10 / -35.11; whitelist: (net, mask) pairs exempt from P6.
     window = slots_per_topic; direct_frac: fraction of the undirected edges
     made direct peers on both ends (WithDirectPeers); topic0_frac: fraction of
     the messages forced onto topic 0; burst = (node, count, hop): `count` more
@@ -123,6 +126,12 @@ def gossipsub_scored(lib, n=300, k=20, topics=1, seed=3, msgs=300, hb=12, flood=
         for t in range(topics):
             subs |= (rng.random(n) < sub_frac).astype(np.uint64) << np.uint64(t)
     sp = eth2_peer_score_params(topics)
+    if ip_threshold is not None:
+        sp.IPColocationFactorThreshold = ip_threshold
+    if ip_weight is not None:
+        sp.IPColocationFactorWeight = ip_weight
+    if whitelist is not None:
+        extra = tuple(extra) + (WithIPWhitelist(whitelist),)
     thr = eth2_thresholds()
     app = np.zeros(n)
     if app_neg_frac:
@@ -1179,3 +1188,166 @@ def _win(fam, d=0, **over):
 WINDOW_EDGE = {fam + "_edge": _win(fam) for fam in WINDOW_FAMILIES}
 WINDOW_OVER = {fam + "_over": _win(fam, 1) for fam in WINDOW_FAMILIES}
 SCENARIOS.update(WINDOW_EDGE)
+
+
+# ---------------------------------------------------------------- P6 under churn
+# The IP colocation factor (score.go:335-379) with observers over the
+# threshold, recounted while connections come and go: every other family keeps
+# each observer at or under IPColocationFactorThreshold peers per IP, so its P6
+# is zero throughout.  A recount moves the scores of the *other* peers on the
+# IP (the "siblings" of the connection that changed), whose own state no event
+# touched.  tests/test_p6.py pins, on the oracle, that these runs hold the
+# sibling changes they are there for; tests/test_p6_gpu.py compares the engine
+# with the oracle after every hop.
+P6_NET = 10 << 24
+P6_HEAVY = dict(ip_groups=5, ip_threshold=3, ip_weight=-35.11)  # a step of the count crosses every threshold
+P6_LIGHT = dict(ip_groups=4, ip_threshold=2, ip_weight=-0.05)   # P6 of the size of P1 + P2: signs flip
+
+
+def p6_churn(lib, n=120, k=16, topics=1, seed=111, msgs=300, hb=12, ip_groups=5, ip_threshold=3, ip_weight=-35.11,
+             retain=Second, dormant_frac=0.3, drops=3, whitelist=None, leaves=0, params=None, churn_nodes=None,
+             extra=(), graph=None, authors=()):
+    """Eth2 scoring with `ip_groups` IPs drawn over the nodes and P6 of the given
+    threshold and weight; RetainScore `retain`.  dormant_frac of the
+    connections start down (no record) and come up at a random hop in 12..89;
+    `drops` of the others go down every 3 hops and return 5-39 hops later
+    (a positive score drops the record at once, any other is retained and
+    expires at the first refresh past `retain`); leaves: topics left per 3 hops
+    and re-joined 3-29 hops later, as churn_scored does.  whitelist: (net,
+    mask) pairs; churn_nodes: only connections of these nodes change.
+    e.conn_events lists the connection events as (hop, a, b)."""
+    rng = np.random.default_rng(seed)
+    n, g = _graph(graph, n, k, seed)
+    sp = eth2_peer_score_params(topics)
+    sp.IPColocationFactorThreshold, sp.IPColocationFactorWeight, sp.RetainScore = ip_threshold, ip_weight, retain
+    ipv4 = (rng.integers(0, ip_groups, n) + P6_NET).astype(np.uint32)
+    pairs = _pairs_of(g, range(n) if churn_nodes is None else churn_nodes)
+    asleep = rng.random(len(pairs)) < dormant_frac
+    dormant = [pairs[i] for i in np.flatnonzero(asleep)]
+    live = [pairs[i] for i in np.flatnonzero(~asleep)]
+    opts = [WithPeerScore(sp, eth2_thresholds()), WithRecordDeliveries(), WithSeed(seed), WithHop(HOP),
+            WithMessageWindow(512), WithDormant(dormant)]
+    if params is not None:
+        opts.append(WithGossipSubParams(params))
+    if whitelist is not None:
+        opts.append(WithIPWhitelist(whitelist))
+    e = NewGossipSub(n, topics, g, graphs.all_subscribed(n, topics), *opts, *extra, ipv4=ipv4, lib=lib)
+    ev = [(int(rng.integers(12, 90)), GS_EV_CONNECT, a, b) for a, b in dormant]
+    for h in range(12, hb * 10 - 10, 3):
+        for i in rng.choice(len(live), drops, replace=False):
+            a, b = live[i]
+            ev.append((h, GS_EV_DISCONNECT, a, b))
+            ev.append((h + int(rng.integers(5, 40)), GS_EV_CONNECT, a, b))
+        for _ in range(leaves):
+            a, t = int(rng.integers(0, n)), int(rng.integers(0, topics))
+            ev.append((h, GS_EV_LEAVE, a, t))
+            ev.append((h + int(rng.integers(3, 30)), GS_EV_JOIN, a, t))
+    ev.sort(key=lambda x: x[0])
+    e.schedule_events([x[1] for x in ev], [x[2] for x in ev], [x[3] for x in ev], [x[0] for x in ev])
+    e.conn_events = [(h, a, b) for h, kd, a, b in ev if kd in (GS_EV_CONNECT, GS_EV_DISCONNECT)]
+    src = rng.integers(0, n, msgs).astype(np.int32)
+    top = rng.integers(0, topics, msgs).astype(np.int32)
+    hops = (5 + (np.arange(msgs) * (hb * 10 - 20)) // msgs).astype(np.int64)
+    _set_authors(src, authors)
+    e.publish(src, top, hops)
+    e.sched_src, e.sched_top, e.sched_hops = src, top, hops
+    return e, hb * 10 + 5
+
+
+P6_FLIP_W, P6_FLIP_APP = -0.05, 0.1
+
+
+def p6_flip(lib, expiry=True, seed=121, extra=()):
+    """A sign flip made by a recount alone, built by hand on a 40-node graph of
+    degree 8.  Observer 0 has threshold + 1 = 3 connected peers on one IP: X
+    (app score -1) and the siblings S1 and S2 (app score +0.1), and a fourth,
+    Y, on a connection that starts down; every other node has an IP of its
+    own.  P6 weighs -0.05: with three records on the IP a sibling's score is
+    0.1 - 0.05 + P1 > 0, so host 0's Join takes S1 and S2 into its mesh (its six
+    peers of score >= 0 are exactly D), with four it is 0.1 - 0.2 + P1 < 0 (P1
+    stays under 0.01, and until hop 45 host 0 writes every message itself, so
+    no peer earns P2 from it).
+    expiry: heartbeats fall on the refresh hops (HeartbeatInitialDelay 1 s).
+    X disconnects at hop 25 (score < 0: the record is retained for 1 s, to
+    3.5 s), Y connects at hop 33 (the siblings fall below 0, and no heartbeat
+    sees it), and the refresh of hop 40, the first past the expiry, drops X's
+    record: the siblings are at >= 0 again when that hop's heartbeat looks for
+    mesh peers of negative score.
+    not expiry (the mirror): the default heartbeat (hops 1, 11, ...), X stays,
+    Y connects at hop 31: the siblings fall below 0 at the hop of a heartbeat,
+    which prunes them.
+    e.flip_edges: host 0's edges to S1 and S2; e.flip_hop: 40 or 31."""
+    n, k = 40, 8
+    g = graphs.random_regular(n, k, seed)
+    rowptr, col, _ = g
+    nb = [int(v) for v in col[rowptr[0]:rowptr[1]]]
+    x, s1, s2, y = nb[:4]
+    ipv4 = (np.arange(n) + P6_NET + 256).astype(np.uint32)
+    ipv4[[x, s1, s2, y]] = P6_NET + 1
+    app = np.zeros(n)
+    app[x] = -1.0
+    app[[s1, s2]] = P6_FLIP_APP
+    sp = eth2_peer_score_params(1)
+    sp.IPColocationFactorThreshold, sp.IPColocationFactorWeight, sp.RetainScore = 2, P6_FLIP_W, Second
+    opts = [WithPeerScore(sp, eth2_thresholds()), WithRecordDeliveries(), WithSeed(seed), WithHop(HOP),
+            WithMessageWindow(128), WithDormant([(0, y)])]
+    if expiry:
+        opts.append(WithGossipSubParams(GossipSubParams(HeartbeatInitialDelay=Second)))
+        ev = [(25, GS_EV_DISCONNECT, 0, x), (33, GS_EV_CONNECT, 0, y)]
+    else:
+        ev = [(31, GS_EV_CONNECT, 0, y)]
+    e = NewGossipSub(n, 1, g, graphs.all_subscribed(n, 1), *opts, *extra, app_score=app, ipv4=ipv4, lib=lib)
+    e.schedule_events([x_[1] for x_ in ev], [x_[2] for x_ in ev], [x_[3] for x_ in ev], [x_[0] for x_ in ev])
+    e.conn_events = [(h, a, b) for h, _, a, b in ev]
+    rng = np.random.default_rng(seed)
+    src = np.concatenate([np.zeros(20, np.int32), rng.integers(0, n, 40).astype(np.int32)])
+    hops = np.concatenate([5 + 2 * np.arange(20), 50 + np.arange(40)]).astype(np.int64)
+    e.publish(src, np.zeros(60, np.int32), hops)
+    e.sched_src, e.sched_hops = src, hops
+    e.flip_edges = [int(rowptr[0]) + nb.index(s1), int(rowptr[0]) + nb.index(s2)]
+    e.flip_hop = 40 if expiry else 31
+    return e, 105
+
+
+def _p6_ladder(lib, x=()):
+    # hubs of degree 64 .. 31 see 8 to 16 peers per IP, whole rows over the
+    # threshold; the churn is on the hubs' connections (a quarter start down)
+    return p6_churn(lib, seed=117, ip_groups=4, ip_threshold=3, ip_weight=-0.002, dormant_frac=0.25,
+                    churn_nodes=range(12), graph=ladder_graph(), authors=LADDER_AUTHORS, extra=x)
+
+
+_P6_WL = [(P6_NET + 1, 0xFFFFFFFF)]  # the second of the drawn IPs
+P6 = {
+    # no churn: the host-side count at the start (most observers hold more
+    # than 10 peers of one IP), and one of the two IPs whitelisted.  Half the
+    # network graylists the other half, so messages reach their last hosts by
+    # gossip, up to 52 hops after their publish on the oracle (37 with the
+    # whitelist): past the 30 hops of the engine's honest message window.  An
+    # accepting validator with an unbounded queue changes no result and gives
+    # the engine its long window (130 hops), as in win_adv; no event is
+    # scheduled, so k_p6 is never launched.
+    "p6_static_dense": lambda lib, x=(): gossipsub_scored(lib, n=200, ip_groups=2, seed=9, app_neg_frac=0.1,
+                                                          extra=(WithValidation([1], 0),) + tuple(x)),
+    "p6_static_whitelist": lambda lib, x=(): gossipsub_scored(lib, n=200, ip_groups=2, seed=9, app_neg_frac=0.1,
+                                                              whitelist=_P6_WL,
+                                                              extra=(WithValidation([1], 0),) + tuple(x)),
+    "p6_churn_heavy": lambda lib, x=(): p6_churn(lib, seed=111, **P6_HEAVY, extra=x),
+    "p6_churn_light": lambda lib, x=(): p6_churn(lib, seed=112, **P6_LIGHT, extra=x),
+    # the whitelist inside k_p6's recount
+    "p6_churn_light_wl": lambda lib, x=(): p6_churn(lib, seed=112, **P6_LIGHT, whitelist=_P6_WL, extra=x),
+    # two topics with leaves and joins beside the connection churn
+    "p6_churn_2t": lambda lib, x=(): p6_churn(lib, seed=113, topics=2, leaves=2, **P6_HEAVY, extra=x),
+    "p6_expiry_flip": lambda lib, x=(): p6_flip(lib, True, extra=x),
+    "p6_connect_flip": lambda lib, x=(): p6_flip(lib, False, extra=x),
+    # degree 40 (gossipsub_dense_dhi's shape): meshes over Dhi and opportunistic
+    # grafting every third heartbeat while P6 moves.  About 10 peers per IP
+    # and observer: threshold 8 keeps P6 of the size of P1 + P2.  (Every seed
+    # has meshes over Dhi at the first heartbeat, on the GRAFTs that answer
+    # the Joins; of seeds 115-130 this one has most heartbeats that find one
+    # later, once connections come and go: hops 21, 41, 51 and 61)
+    "p6_dhi": lambda lib, x=(): p6_churn(lib, n=120, k=40, seed=125, msgs=200, hb=20, ip_groups=4, ip_threshold=8,
+                                         ip_weight=-0.05, params=GossipSubParams(OpportunisticGraftTicks=3), extra=x),
+    # k_p6's lane loop on rows of 64, 63, 33, 32, 31, 1 and 0 edges
+    "ladder_p6_churn": _p6_ladder,
+}
+SCENARIOS.update(P6)

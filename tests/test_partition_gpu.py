@@ -161,6 +161,18 @@ def run_partitioned(world, name, oracle):
     # at age maxAge, slots are used again at retireHops
     (2, "win_gossip_edge"),
     (3, "win_flood_edge"),
+    # P6 over its threshold: the host-side count at the start, and k_p6's
+    # recounts under churn, which every rank runs over its own observers
+    (2, "p6_static_dense"),
+    (2, "p6_static_whitelist"),
+    (2, "p6_churn_heavy"),
+    (2, "p6_churn_light"),
+    (2, "p6_churn_light_wl"),
+    (2, "p6_churn_2t"),
+    (2, "p6_expiry_flip"),
+    (2, "p6_connect_flip"),
+    (2, "p6_dhi"),
+    (2, "ladder_p6_churn"),
 ])
 def test_partitioned_engine_matches_oracle(world, name, oracle_path):
     res = run_partitioned(world, name, oracle_path)

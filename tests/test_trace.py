@@ -242,6 +242,27 @@ def test_gpu_trace_equals_oracle(oracle_path, name):
     check_invariants(e, got, nodes)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["p6_churn_heavy", "p6_expiry_flip", "p6_connect_flip"])
+def test_gpu_trace_equals_oracle_under_p6_recounts(oracle_path, name):
+    """P6 recounted under churn (scenarios.P6): the traced hosts' Graft / Prune
+    events hop by hop are what a stale score memo would change.  Host 0 is the
+    observer of the two flip scenarios.  (check_invariants counts one AddPeer
+    per edge, which churn breaks, so the streams alone are compared.)"""
+    nodes = [0, 3, 17] if name.endswith("_flip") else traced_nodes(name)
+    _, ref = traced_run(oracle_path, name, nodes)
+    _, got = traced_run(PRODUCT_LIB, name, nodes)
+    want = {T("ADD_PEER"), T("GRAFT")}
+    if name != "p6_connect_flip":  # (its only event is a connect)
+        want.add(T("REMOVE_PEER"))
+    if name != "p6_expiry_flip":  # (its point is that host 0 must not prune)
+        want.add(T("PRUNE"))
+    assert want <= set(ref["type"].tolist())
+    assert len(got) == len(ref), (len(got), len(ref))
+    bad = np.nonzero(got != ref)[0]
+    assert len(bad) == 0, f"{len(bad)} events differ, first {got[bad[0]]} vs {ref[bad[0]]}"
+
+
 def _window_edge_trace(oracle_path):
     """win_gossip_edge's oracle stream of the tail's tip, its neighbour and
     node 0, its invariants checked on the oracle's engine (which reads back
