@@ -59,9 +59,6 @@
 #define GS_OCC_PB
 #endif
 #define GS_MAX_WPL 4   // words per lane in the node-wave kernels: W <= 256
-#ifndef GS_SBATCH
-#define GS_SBATCH 2    // edge_scores_batch: edges whose loads are in flight together (<= 4)
-#endif
 #define GS_QCAP 320    // phase A delivery queue (>= 63 pending + 256 appended per sub-round)
 #define GS_BMAP 32     // phase A: list blocks mapped to senders without a search (64 per entry)
 // push arena: a region of this many 16-bit slots per owned sender
@@ -397,10 +394,6 @@ __device__ __forceinline__ int spam_incr(const Dev& d, int row, int slot) {
   if (c > d.GR + 1) atomicSub(w, 1u << sh);
   return c;
 }
-__device__ __forceinline__ int spam_count(const Dev& d, int row, int slot) {
-  const uint32_t x = __hip_atomic_load(spam_word(d, row, slot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return (int)((x >> ((slot & 7) * 4)) & 0xF);
-}
 // count one or more RPCs of `bytes` in total sent over the sender's edge e
 __device__ __forceinline__ void acct_send(const Dev& d, int64_t e, int64_t bytes, int n) {
   d.rpcB[e] += (unsigned long long)bytes;
@@ -667,15 +660,6 @@ __device__ __forceinline__ void dlt_put(const Dev& d, int64_t i, uint32_t q) {
 }
 // the same with the layout known at compile time (the streaming refresh)
 template <bool NDLT>
-__device__ __forceinline__ uint32_t dlt_get_t(const Dev& d, int64_t i) {
-  if constexpr (NDLT) {
-    const uint32_t x = d.dltN[i];
-    return (x & 0xFFu) | ((x >> 8) << 16);
-  } else {
-    return d.dlt[i];
-  }
-}
-template <bool NDLT>
 __device__ __forceinline__ void dlt_put_t(const Dev& d, int64_t i, uint32_t q) {
   if constexpr (NDLT) d.dltN[i] = (uint16_t)((q & 0xFFu) | ((q >> 16) << 8));
   else d.dlt[i] = q;
@@ -793,59 +777,6 @@ __device__ __forceinline__ double edge_score_wave(const Dev& d, int64_t e, doubl
   return has_record(d, e) ? score_tail_v(d, score, app, p6, b) : 0.0;
 }
 
-// edge_score_wave for every edge rowBase + j with bit j of `mask` (wave-
-// uniform): GS_SBATCH edges per pass with all their loads in flight at once (lane
-// = topic), instead of one memory round trip per edge.  Lane j receives its
-// edge's score in S; other lanes keep theirs.  lds: 4 * 64 doubles.
-__device__ __forceinline__ void edge_scores_batch(const Dev& d, int64_t rowBase, unsigned long long mask, double& S,
-                                                  double* lds) {
-  const int lane = lane_id();
-  const bool mine = (mask >> lane) & 1;
-  if (!d.scoring) {
-    if (mine) S = 0.0;
-    return;
-  }
-  const int T = d.T;
-  const int tl = lane < T ? lane : 0;
-  const bool sc = lane < T && d.tp[tl].scored;
-  const uint64_t scoredT = __ballot(sc);
-  double app = 0.0, p6 = 0.0, b = 0.0;
-  bool rec = false;
-  if (mine) {  // the tail inputs of the lane's own edge
-    const int64_t e = rowBase + lane;
-    app = d.app[d.col[e]];
-    p6 = d.p6[e];
-    b = d.bp[e];
-    rec = has_record(d, e);
-  }
-  while (mask) {
-    int js[GS_SBATCH];
-#pragma unroll
-    for (int k = 0; k < GS_SBATCH; ++k) {
-      js[k] = mask ? __ffsll((long long)mask) - 1 : -1;
-      mask &= mask ? mask - 1 : 0ull;
-    }
-    TermIn x[GS_SBATCH];
-#pragma unroll
-    for (int k = 0; k < GS_SBATCH; ++k) x[k] = term_load(d, tix(d, tl, rowBase + (js[k] < 0 ? js[0] : js[k])));
-    __syncthreads();  // the previous pass's sums are done with lds
-#pragma unroll
-    for (int k = 0; k < GS_SBATCH; ++k) lds[k * 64 + lane] = (js[k] >= 0 && sc) ? term_eval(d.tp[tl], x[k]) : 0.0;
-    __syncthreads();
-    int kb = -1;
-#pragma unroll
-    for (int k = 0; k < GS_SBATCH; ++k)
-      if (lane == js[k]) kb = k;
-    if (kb >= 0) {
-      double score = 0.0;
-      for (int t = 0; t < T; ++t)
-        if ((scoredT >> t) & 1) score += lds[kb * 64 + t];
-      S = rec ? score_tail_v(d, score, app, p6, b) : 0.0;
-    }
-  }
-  __syncthreads();
-}
-
 // peerScore.Graft — score.go:640-658 (scored topics only)
 __device__ __forceinline__ void stats_graft(const Dev& d, int64_t e, int t, int64_t now) {
   if (!d.scoring || !d.tp[t].scored) return;
@@ -890,10 +821,6 @@ __device__ __forceinline__ void add_backoff(const Dev& d, int64_t e, int t, int6
   d.boMask[e] |= 1ull << t;  // the edge's observer only: no other wave writes it
 }
 
-// ---- slot-id arena: compact IWANT request / response payloads ----------
-// Writes the set bits of a wave-distributed bitset (word w = lane + 64*j) as
-// slot ids in ascending slot order (phase A walks them with a cursor);
-// returns the packed record (off << 24 | count) or -1 when empty.
 // Inclusive prefix sum over the 64 lanes with DPP row shifts and row
 // broadcasts (no LDS permutes).  Call with all 64 lanes active.
 __device__ __forceinline__ int wave_incl_sum(int x) {
@@ -909,61 +836,8 @@ __device__ __forceinline__ int wave_incl_sum(int x) {
 __device__ __forceinline__ int lane_rank(uint64_t m) {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
-// Former LDS rank-loop variant (kept for its call sites): now select_k.
-__device__ __forceinline__ bool select_k_lds(bool cand, uint64_t key, int k, uint64_t* skey) {
-  (void)skey;  // the radix selection needs no LDS
-  return select_k(cand, key, k);
-}
-
 // Value of lane 63 (wave-uniform).
 __device__ __forceinline__ int wave_last(int x) { return __builtin_amdgcn_readlane(x, 63); }
-
-template <int WPL>
-__device__ __forceinline__ int64_t arena_write(const Dev& d, int buf, const uint64_t (&bits)[WPL]) {
-  const int lane = lane_id();
-  int incl[WPL], tot[WPL];
-  int total = 0;
-#pragma unroll
-  for (int j = 0; j < WPL; ++j) {
-    const int c = __popcll(bits[j]);
-    const int s = wave_incl_sum(c);  // inclusive prefix over lanes of word row j
-    incl[j] = s - c;
-    tot[j] = wave_last(s);
-    total += tot[j];
-  }
-  if (total == 0) return -1;
-  unsigned long long off = 0;
-  if (lane == 0) off = pool_take(d, buf, (unsigned long long)total);
-  off = lane_get64(off, 0);
-  if (off == ~0ull) return -1;
-  int rowBase = (int)off;
-#pragma unroll
-  for (int j = 0; j < WPL; ++j) {
-    int pos = rowBase + incl[j];
-    uint64_t y = bits[j];
-    while (y) {
-      const int b = __ffsll((long long)y) - 1;
-      y &= y - 1;
-      d.pool[buf][pos++] = (lane + 64 * j) * 64 + b;
-    }
-    rowBase += tot[j];
-  }
-  return ((int64_t)off << 24) | (int64_t)total;
-}
-
-// Expands an arena record into the wave's LDS bitset lds[0..W).
-__device__ __forceinline__ void arena_read(const Dev& d, int buf, int64_t rec, unsigned long long* lds) {
-  const int lane = lane_id();
-  for (int w = lane; w < d.W; w += 64) lds[w] = 0;
-  __syncthreads();
-  const int64_t off = rec >> 24;
-  const int n = (int)(rec & 0xFFFFFF);
-  for (int k = lane; k < n; k += 64) {
-    const int slot = d.pool[buf][off + k];
-    atomicOr(&lds[slot >> 6], 1ull << (slot & 63));
-  }
-  __syncthreads();
-}
 
 // The k-th smallest (key, id) of a candidate set spread over the wave: radix
 // select on the 64-bit key (8 passes of 8-bit digits, a 256-bin LDS

@@ -1203,7 +1203,6 @@ void gs_engine::heartbeat(const Hop& hp) {
   // by hb_pre so it computes their exact scores too
   const bool exactPass = scoring && (refreshedHop == h || ticks % (uint64_t)d.OGT == 0);
   if (no) TIMED(this, GS_K_HB_PRE, (k_hb_pre<<<no, 64, 0, stream>>>(d, now, ticks, scoring && !exactPass ? 1 : 0)));
-  const int allExact = 1;
   if (scoring && refreshedHop == h)
     TIMED(this, GS_K_SCORE, (score_rows<3>(d, eOwn, T, nullptr, stream)));
   else if (scoring && ticks % (uint64_t)d.OGT == 0)
@@ -1214,7 +1213,7 @@ void gs_engine::heartbeat(const Hop& hp) {
   // nodes of degree <= 32: two topics per wave (one per half-wave)
   if (no)
     TIMED(this, GS_K_HEARTBEAT, with_consts([&](auto half) {
-            k_heartbeat<CV(half)><<<no, 64, 0, stream>>>(d, h, now, ticks, hp.cur, head, newhead, allExact);
+            k_heartbeat<CV(half)><<<no, 64, 0, stream>>>(d, h, now, ticks, hp.cur, head, newhead);
           }, Flag{d.maxDeg <= 32}));
   // the peertx counters of the window that left the cache (pre-shift HL - 1)
   if (no) {

@@ -256,4 +256,3 @@ __global__ void k_xp_unpack(Dev d, int cur, const PRec* __restrict__ in, int64_t
   d.ibxRec[cur][p.ri] = p.n < 0 ? -1 : (((slotBase + p.off) << 24) | (int64_t)p.n);
 }
 
-__global__ void k_set_u64(unsigned long long* p, unsigned long long v) { *p = v; }

@@ -49,8 +49,9 @@
 //   MODE 4: heartbeat memo -> score1 without a refresh in this hop: exact where
 //     a score-lowering change happened or S0 < 0, else S0 (a lower bound >= 0
 //     of the exact score, so every heartbeat threshold test — 0, Gossip- and
-//     PublishThreshold, all <= 0 — decides exactly).  k_heartbeat recomputes
-//     the few scores it needs as values (Dhi ranking) from the same rule.
+//     PublishThreshold, all <= 0 — decides exactly).  The few scores that
+//     k_heartbeat compares as values (Dhi ranking) are exact too: k_hb_pre's
+//     flagDhi marks those edges dirty before this pass.
 #define GS_SB 8   // passes per load batch
 #ifndef GS_RB
 #define GS_RB 4   // refresh: pairs per lane in flight (the ring's register sets)
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(64) void k_score_rows(Dev d, double* __restrict__ o
 // own stores may alias that table, so every field would be loaded again after
 // every store (17 extra vector loads per pair, each under a full wait).
 // LANE_T: T divides 64, so a lane's topic is fixed (lane % T) and a by-value
-// copy of its params stays in registers; otherwise (or with GS_RF_TPLDS) they
+// copy of its params stays in registers; otherwise they
 // come from a field-major LDS copy of the table, indexed by the pair's topic.
 // mfp is read only where flag bit 2 says it may be non-zero (GS_FL_MFP: a few
 // hundred pairs of 2e9 at config4), by a wave-uniform branch.
@@ -178,12 +179,6 @@ __global__ __launch_bounds__(64) void k_score_rows(Dev d, double* __restrict__ o
 // are not decayed and expire; the honest instantiation carries none of it.
 #ifndef GS_RG
 #define GS_RG 8  // refresh: groups per wave
-#endif
-#ifndef GS_RF_TPLDS
-#define GS_RF_TPLDS 0  // timing A/B: 1 keeps the topic params in LDS for every T
-#endif
-#ifndef GS_RF_MFPBIT
-#define GS_RF_MFPBIT 1  // timing A/B: 0 streams mfp with the other arrays
 #endif
 #define GS_RS (GS_RP / 64)  // slots of a group
 constexpr int GS_TPW = (int)(sizeof(TopicP) / 8);
@@ -204,7 +199,7 @@ __device__ __forceinline__ X& at_u(X* base, unsigned c) {
   return *(X*)((char*)base + (size_t)(c * (unsigned)sizeof(X)));
 }
 struct RfIn {  // one pair's state as loaded
-  double fmd, mmd, mfp, imd;
+  double fmd, mmd, imd;  // (mfp is read only where GS_FL_MFP is set)
   int64_t gt;
   uint32_t q;    // wide pending counts
   uint16_t qn;   // narrow ones, packed as stored
@@ -213,10 +208,8 @@ struct RfIn {  // one pair's state as loaded
 template <bool CHURN, bool LANE_T, bool NDLT>
 __global__ __launch_bounds__(64) GS_OCC_RF void k_refresh_rows(Dev d, int64_t now) {
   static_assert(GS_RS % GS_RB == 0, "a ring turn stays within one group");
-  constexpr bool TP_REG = LANE_T && !GS_RF_TPLDS;
-  constexpr bool MFPBIT = GS_RF_MFPBIT != 0;
   __shared__ double sT[GS_RP + GS_RP / 64];
-  __shared__ uint64_t sTp[TP_REG ? 1 : GS_TPW][64];  // [field][topic]: conflict-free 64-bit reads
+  __shared__ uint64_t sTp[LANE_T ? 1 : GS_TPW][64];  // [field][topic]: conflict-free 64-bit reads
   const int lane = lane_id();
   const int T = d.T;
   const int epw = GS_RP / T;     // edges of a group
@@ -230,7 +223,7 @@ __global__ __launch_bounds__(64) GS_OCC_RF void k_refresh_rows(Dev d, int64_t no
   const uint64_t scoredT = __ballot(lane < T && d.tp[tl].scored);
   const int tLane = LANE_T ? (lane & (T - 1)) : 0;
   TopicP tpR{};
-  if constexpr (TP_REG) {
+  if constexpr (LANE_T) {
     tpR = d.tp[tLane];
   } else {
     if (lane < T) {
@@ -257,7 +250,6 @@ __global__ __launch_bounds__(64) GS_OCC_RF void k_refresh_rows(Dev d, int64_t no
     else x.q = at_u(d.dlt + pB, c);
     x.fmd = at_u(d.fmd + pB, c);
     x.mmd = at_u(d.mmd + pB, c);
-    x.mfp = MFPBIT ? 0.0 : at_u(d.mfp + pB, c);
     x.imd = d.anyImd ? at_u(d.imd + pB, c) : 0.0;
     x.gt = at_u(d.graftTime + pB, c);
     x.fl = at_u(d.flags + pB, c);
@@ -304,8 +296,7 @@ __global__ __launch_bounds__(64) GS_OCC_RF void k_refresh_rows(Dev d, int64_t no
             pair_split(d, i, e, t);
             if (LANE_T) t = tLane;
           }
-          if constexpr (LANE_T && !TP_REG) asm volatile("" : "+v"(t));  // (keeps the A/B's reads in LDS)
-          const TopicP tp = TP_REG ? tpR : tp_from_lds(sTp, t);
+          const TopicP tp = LANE_T ? tpR : tp_from_lds(sTp, t);
           const bool act = (scoredT >> t) & 1;
           double term = 0.0;
           uint8_t st = 1;
@@ -330,10 +321,10 @@ __global__ __launch_bounds__(64) GS_OCC_RF void k_refresh_rows(Dev d, int64_t no
             x.mm = v;
             x.fl = r.fl;
             x.mfp = 0.0;
-            if (!MFPBIT || (r.fl & GS_FL_MFP)) {
-              // (MFPBIT: rare, so the branch is skipped by nearly every wave;
-              // the load and its wait stay inside it)
-              const double m = MFPBIT ? at_u(d.mfp + p0, ul) : r.mfp;
+            if (r.fl & GS_FL_MFP) {
+              // (rare, so the branch is skipped by nearly every wave; the load
+              // and its wait stay inside it)
+              const double m = at_u(d.mfp + p0, ul);
               v = m * tp.MfpDecay;
               if (v < d.DecayToZero) v = 0;
               if (v != m) at_u(d.mfp + p0, ul) = v;
@@ -687,30 +678,9 @@ __device__ __forceinline__ int wm_rank(const WMask& a, int w) {
   return r + __popcll(a.m[w >> 6] & ((1ull << (w & 63)) - 1));
 }
 
-// Exclusive prefix-OR of a 64-bit value over ascending lanes (lane 0 gets 0).
-__device__ __forceinline__ uint64_t wave_prefix_or_excl(uint64_t x) {
-  const int lane = lane_id();
-  uint64_t incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = shfl_u64(incl, (lane - o) & 63);
-    if (lane >= o) incl |= y;
-  }
-  const uint64_t prev = shfl_u64(incl, (lane - 1) & 63);
-  return lane == 0 ? 0ull : prev;
-}
-
 __device__ __forceinline__ unsigned long long wave_sum_ll(long long v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return (unsigned long long)v;
-}
-
-__device__ __forceinline__ int wave_min_int(int x) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const int y = __shfl_xor(x, o);
-    x = y < x ? y : x;
-  }
-  return x;
 }
 
 #define GS_NO_SLOT 0x7FFFFFFF
@@ -979,10 +949,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
     else if (irN) nSrvRpc = 1;
   }
   // per-sender view for the block-parallel walk
-#ifndef GS_PB8
-#define GS_PB8 1  // timing A/B: -DGS_PB8=0 reads pushed segments 4 slots (8 B) per block
-#endif
-  constexpr int EPBP = GS_PB8 ? 8 : 4;  // slots per block of a pushed segment (16 B: 8 slots)
+  constexpr int EPBP = 8;  // slots per block of a pushed segment (16 B)
   // 16-byte blocks of the sender's list (4 entries) or pushed segment (8 slots)
   const int nb = pOff >= 0 ? (Ln + EPBP - 1) / EPBP : (Ln + 3) >> 2;
   const int bincl = wave_incl_sum(nb);
@@ -1012,11 +979,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
   // words of the active window; none of them is written before this wave's
   // own passes 2b / 3
   constexpr int PF3 = 16;
-#ifndef GS_PF
-#define GS_PF 1  // timing A/B: -DGS_PF=0 builds the phase A without the prefetch
-#endif
-  constexpr bool kPf = GS_PF != 0;
-  const int nWdPf = (kPf && NARROW && scoring && d.dltN != nullptr) ? (deg * T) >> 1 : 0;
+  const int nWdPf = (NARROW && scoring && d.dltN != nullptr) ? (deg * T) >> 1 : 0;
   const bool pf3 = nWdPf > 0 && nWdPf <= 64 * PF3;
   uint32_t q3[PF3];
   if (pf3) {
@@ -1033,7 +996,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
   for (int j = 0; j < WPL; ++j) {
     const int w = lane + 64 * j;
     Sp[j] = Hp[j] = Op[j] = 0;
-    if constexpr (!ADV && kPf) {
+    if constexpr (!ADV) {
       const bool act = w < W && wm_has(amR, w);
       if (act || (w < W && wm_has(amP, w))) Sp[j] = d.seen[(int64_t)v * W + w];
       if (act) {
@@ -1136,15 +1099,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
   // are compacted into an LDS queue and handed to fn 64 at a time by all lanes.
   // fn(i, slot) sees every sent, non-graylisted copy; walk() also counts
   // nSent / nGray when `count` (the first walk).
-  // block kb of sender i: four list entries (16 B), or four pushed slots (8 B)
+  // block kb of sender i: four list entries or eight pushed slots (16 B)
   const uint32_t* const flPrv = prv ? d.fl[1] : d.fl[0];
   const uint16_t* const ibxPrv = prv ? d.ibx[1] : d.ibx[0];
   auto load_block = [&](int i, int kb) -> uint4 {
-    if ((pushM >> i) & 1) {
-      if constexpr (EPBP == 8) return *(const uint4*)(ibxPrv + 8 * (size_t)sAddr[i] + 8 * kb);
-      const uint2 p = *(const uint2*)(ibxPrv + 8 * (size_t)sAddr[i] + 4 * kb);
-      return make_uint4(p.x, p.y, 0u, 0u);
-    }
+    if ((pushM >> i) & 1) return *(const uint4*)(ibxPrv + 8 * (size_t)sAddr[i] + 8 * kb);
     return *(const uint4*)(flPrv + (size_t)sAddr[i] + 4 * kb);
   };
   auto walk = [&](auto&& fn, bool count) {
@@ -1248,7 +1207,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
         // c-major positions (delivery order does not matter: every update is
         // a commutative LDS atomic), four entries per lane between drains
         // (the queue holds 63 pending + 256 appended)
-        const bool wideAny = EPBP > 4 && __ballot(wide) != 0;
+        const bool wideAny = __ballot(wide) != 0;
 #pragma unroll
         for (int g = 0; g < EPBP / 4; ++g) {
           if (g > 0 && !wideAny) break;
@@ -1502,7 +1461,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
     rkw[j] = 0;
     const bool ret = w < W && wm_has(amP, w);
     if (ret) Rw[j] = d.pubmask[cur][w];
-    if constexpr (!ADV && kPf) {
+    if constexpr (!ADV) {
       Sw[j] = Sp[j];  // (prefetched at wave start)
       if (w < W && wm_has(amR, w)) {
         rkw[j] = wm_rank(amR, w);
@@ -1782,11 +1741,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
       uint32_t* const pw = (uint32_t*)(d.dltN + base * T);
       const int q128 = 128 / T, r128 = 128 - q128 * T;
       int ic = (2 * lane) / T, tc = 2 * lane - ((2 * lane) / T) * T;
-#ifndef GS_UPD2P
-#define GS_UPD2P 1  // timing A/B: -DGS_UPD2P=0 updates the two pairs of a word one after the other
-#endif
       auto upd2 = [&](int wi, int i, int t, uint32_t q) -> uint32_t {
-        if (GS_UPD2P && !hasUnc) {
+        if (!hasUnc) {
           // both pairs of the word at once, a byte per field: counts
           // [copies | fresh << 8] and pending [fmd | mmd << 8] per 16-bit half;
           // fmd += fresh, mmd += fresh + credited duplicates = copies while in

@@ -1474,15 +1474,39 @@ __global__ __launch_bounds__(64) void k_hb_pre(Dev d, int64_t now, uint64_t tick
   }
 }
 
-// emitGossip (gossipsub.go:1658-1712) for topic t of node v; lanes = edges.
-// The peer filter uses the live Score(p) (:1681): Slive caches it per lane and
-// is recomputed (one wave-parallel score per lane) only after the peer's stats
-// changed earlier in this heartbeat.
-__device__ __forceinline__ uint64_t emit_gossip(const Dev& d, int v, int t, int64_t hop, int head, bool valid,
-                                                int vcol, bool inTopic, bool excl, bool dir, double& Slive,
-                                                bool& dirty, bool& dirtyUp, int64_t rowBase, double* lds,
-                                                int nm) {
-  const int lane = lane_id();
+// emitGossip's peer filter uses the live Score(p) (gossipsub.go:1681): Slive
+// caches it per lane and is recomputed (one wave-parallel score per lane) for
+// the lanes in `want` whose peer's stats changed earlier in this heartbeat.
+// Lane j's edge is rowBase + (j & emask).
+// A graft never lowers a score (P1 is 0 at meshTime 0, the P3 deficit term
+// is switched off; weights validated w1 >= 0, w3 <= 0), so a cached score
+// already at or above the threshold stays a correct decision after one.
+__device__ __forceinline__ void live_refresh(const Dev& d, bool want, int64_t rowBase, int emask, double& Slive,
+                                             bool& dirty, bool& dirtyUp, double* lds) {
+  unsigned long long dm = __ballot(want && (dirty || (dirtyUp && !(Slive >= d.gossipThr))));
+  while (dm) {  // rare (a peer pruned earlier in this heartbeat): one edge at a time
+    const int j = __ffsll((long long)dm) - 1;
+    dm &= dm - 1;
+    const double s = edge_score_wave(d, rowBase + (j & emask), lds);
+    if (lane_id() == j) {
+      Slive = s;
+      dirty = false;
+      dirtyUp = false;
+    }
+  }
+}
+// emitGossip's target for n candidates: max(Dlazy, GossipFactor * n)
+// (gossipsub.go:1686-1690)
+__device__ __forceinline__ int ihave_target(const Dev& d, int n) {
+  const int factor = (int)(d.GossipFactor * (double)n);
+  return factor > d.Dlazy ? factor : d.Dlazy;
+}
+
+// emitGossip (gossipsub.go:1658-1712) for fanout topic t of node v; lanes =
+// edges.  (The joined topics' emitGossip is steps 2 and 3 of hb_topics.)
+__device__ __forceinline__ uint64_t emit_gossip(const Dev& d, int v, int t, int64_t hop, bool valid, int vcol,
+                                                bool inTopic, bool excl, bool dir, double& Slive, bool& dirty,
+                                                bool& dirtyUp, int64_t rowBase, double* lds, int nm) {
   if (nm == 0) return 0;  // nm: message ids of topic t in the gossip windows
   if (behaves(d, v, GS_BEHAVE_NO_FORWARD)) return 0;  // a squatter emits no gossip
   // an IHAVE spammer advertises to every topic peer (mesh, direct, any score)
@@ -1490,29 +1514,14 @@ __device__ __forceinline__ uint64_t emit_gossip(const Dev& d, int v, int t, int6
   // more than MaxIHaveLength ids: each receiver's own keyed subset
   // (gossipsub.go:1702-1709) is cut by the receiver in k_phase_b
   const bool base = valid && inTopic && !excl && !dir;
-  // A graft never lowers a score (P1 is 0 at meshTime 0, the P3 deficit term
-  // is switched off; weights validated w1 >= 0, w3 <= 0), so a cached score
-  // already at or above the threshold stays a correct decision after one.
-  unsigned long long dm = __ballot(base && (dirty || (dirtyUp && !(Slive >= d.gossipThr))));
-  while (dm) {  // rare (a peer pruned earlier in this heartbeat): one edge at a time
-    const int j = __ffsll((long long)dm) - 1;
-    dm &= dm - 1;
-    const double s = edge_score_wave(d, rowBase + j, lds);
-    if (lane == j) {
-      Slive = s;
-      dirty = false;
-      dirtyUp = false;
-    }
-  }
+  live_refresh(d, base, rowBase, 63, Slive, dirty, dirtyUp, lds);
   const bool cand = base && Slive >= d.gossipThr;
   const int n = __popcll(__ballot(cand));
-  int target = d.Dlazy;
-  const int factor = (int)(d.GossipFactor * (double)n);
-  if (factor > target) target = factor;
+  const int target = ihave_target(d, n);
   bool sel = cand;
   if (target < n) {
     const uint64_t key = gs_key64(d.seed, GS_SITE_EMIT_PEERS, v, (uint32_t)hop, vcol, t);
-    sel = select_k_lds(cand, key, target, (uint64_t*)lds);
+    sel = select_k(cand, key, target);
   }
   return sel ? (1ull << t) : 0;
 }
@@ -1523,27 +1532,50 @@ __device__ __forceinline__ int half_count(bool x) {
   return __popc((uint32_t)(b >> (lane_id() & 32)));
 }
 
-// The joined-topic loop of k_heartbeat<true>: pairs of joined topics (ta, tb)
-// ascending, half h = lane >> 5 handles topic (ta, tb)[h] of every edge (lane
-// & 31).  Per pair:
-//   1. mesh maintenance decisions of both topics (they read the heartbeat memo
-//      S and the topic's own mesh / backoff bits only, so the two topics are
-//      independent): negative-score prune, Dlo graft, Dhi prune (serially per
-//      half: it ranks by value through LDS), Dout graft, opportunistic graft;
-//   2. ta's stats writes (peerScore.Prune / Graft, backoff), then emitGossip's
-//      live-score refresh for ta's candidates; tb's writes, then tb's refresh
-//      starting from ta's live-score state — the serial topic order, so every
-//      live score emitGossip compares equals the serial loop's;
-//   3. both topics' IHAVE peer selections (key draw + select) at once.
-__device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int deg, bool vm, int64_t e, int vcol,
-                                        int64_t hop, int64_t now, uint64_t ticks, int head, uint64_t joined,
-                                        uint64_t subv, double S, bool dir, bool ob, bool graftSpam, int nmT,
-                                        uint64_t& meshl, uint64_t& boM, double& Slive, bool& dirty, bool& dirtyUp,
-                                        uint64_t& tograft, uint64_t& toprune, uint64_t& ihave, uint64_t& spamGraft,
-                                        int* plst, int* obs, int* posOf, double* lds, unsigned long long& cyMesh,
-                                        unsigned long long& cyEmit, unsigned long long& cySel) {
+// The topic loop's lane groups: the whole wave, or (PAIR) each half-wave with
+// a topic of its own.  Count and keyed selection within the lane's group.
+template <bool PAIR>
+__device__ __forceinline__ int grp_count(bool x) {
+  if constexpr (PAIR) return half_count(x);
+  else return __popcll(__ballot(x));
+}
+template <bool PAIR>
+__device__ __forceinline__ bool grp_select(bool cand, uint64_t key, int k) {
+  if constexpr (PAIR) return select_k_half(cand, key, k);
+  else return select_k(cand, key, k);
+}
+
+// The joined-topic loop of k_heartbeat: mesh maintenance (gossipsub.go:
+// 1331-1503) and emitGossip's peer selection, per joined topic ascending.
+// A group of lanes handles one topic of every edge: the whole wave (h = 0, one
+// topic per turn), or with PAIR a half-wave (h = lane >> 5 handles topic
+// (ta, tb)[h] of edge lane & 31, two topics per turn).  Per turn:
+//   1. the mesh maintenance decisions of the turn's topics: negative-score
+//      prune, Dlo graft, Dhi prune (one group at a time: it ranks by value
+//      through LDS), Dout graft, opportunistic graft, the GRAFT-spammer rule.
+//      Nothing is written yet.  The decisions read only the heartbeat memo S,
+//      the topic's own mesh and backoff bits, dir and ob, so none depends on
+//      a write of an earlier decision or topic; the one read of d.backoff
+//      (GRAFT spam) is covered by pr, whose new backoff expires after now;
+//   2. per topic in ascending order its stats writes (peerScore.Prune / Graft,
+//      backoff), then emitGossip's live-score refresh for its candidates (with
+//      PAIR, tb's starts from ta's live-score state).  A topic's writes come
+//      before its own refresh and after every earlier topic's: the order of
+//      the reference's loop, which writes at each decision and calls
+//      emitGossip at the end of the topic, so every live score emitGossip
+//      compares is the same;
+//   3. the IHAVE peer selection (key draw + select) of the turn's topics.
+template <bool PAIR>
+__device__ __forceinline__ void hb_topics(const Dev& d, int v, int64_t base, bool vm, int64_t e, int vcol, int64_t hop,
+                                          int64_t now, uint64_t ticks, uint64_t joined, uint64_t subv, double S,
+                                          bool dir, bool ob, bool graftSpam, int nmT, uint64_t& meshl, uint64_t& boM,
+                                          double& Slive, bool& dirty, bool& dirtyUp, uint64_t& tograft,
+                                          uint64_t& toprune, uint64_t& ihave, uint64_t& spamGraft, int* plst, int* obs,
+                                          int* posOf, double* lds, unsigned long long& cyMesh,
+                                          unsigned long long& cyEmit, unsigned long long& cySel) {
+  constexpr int NG = PAIR ? 2 : 1;  // groups per wave
   const int lane = lane_id();
-  const int h = lane >> 5;
+  const int h = PAIR ? lane >> 5 : 0;
   const uint32_t hw = (uint32_t)hop;
   const bool noFwd = behaves(d, v, GS_BEHAVE_NO_FORWARD);
   const bool ihaveSpam = behaves(d, v, GS_BEHAVE_IHAVE_SPAM);
@@ -1554,8 +1586,8 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
   // could be grafted (negative-score prune, Dlo / Dhi / Dout below;
   // opportunistic ticks and GRAFT spammers are never steady).  Counted for
   // every topic at once: lane t of a transposed edge mask holds topic t's
-  // edges (the lower half's edges are all of them).
-  const bool lo = lane < 32 && vm;
+  // edges (PAIR: the lower half's edges are all of them).
+  const bool lo = vm && (!PAIR || lane < 32);
   const uint64_t mL = lo ? meshl : 0ull;
   // graft candidates of getPeers' filter in step 1: topic peers not in the
   // mesh nor in backoff, not direct, score >= 0
@@ -1567,44 +1599,48 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
                      (negT || cntT > d.Dhi || (cntT < d.Dlo && candT) || (cntT >= d.Dlo && outT < d.Dout && obCandT));
   const uint64_t busy = (oppTick || graftSpam) ? ~0ull : __ballot(busyT);
   uint64_t jm = joined;
-  uint64_t myT = 0;  // the topics this half handled
+  uint64_t myT = 0;  // the topics this group handled
   while (jm) {
     const unsigned long long c0 = GS_CLK();
     const int ta = __ffsll((long long)jm) - 1;
     jm &= jm - 1;
-    const int tb = jm ? __ffsll((long long)jm) - 1 : -1;
-    if (jm) jm &= jm - 1;
-    const int t = h ? tb : ta;  // this half's topic, -1: none
+    const int tb = PAIR && jm ? __ffsll((long long)jm) - 1 : -1;
+    if (PAIR && jm) jm &= jm - 1;
+    const int t = h ? tb : ta;  // this group's topic, -1: none
     const bool act = t >= 0;
     const int tt = act ? t : 0;
     const uint64_t bit = act ? 1ull << t : 0ull;
     const bool inTopic = vm && act && ((subv >> tt) & 1);
     bool m = vm && act && (meshl & bit);
-    bool pr = false, gr = false;  // pruned / grafted at t in this pass
-    // both topics steady: step 1 changes nothing (wave-uniform)
+    bool pr = false, gr = false;  // pruned / grafted at t in this turn
+    // the turn's topics are steady: step 1 changes nothing (wave-uniform)
     const bool fast = !((busy >> ta) & 1) && (tb < 0 || !((busy >> tb) & 1));
     if (!fast) {
     // ---- 1. decisions
+    // drop all peers with negative score, without PX; a GRAFT spammer first
+    // leaves its whole mesh (gossipsub_spam_test.go:428-446)
     if (m && (S < 0 || (graftSpam && ticks == 1))) {
       pr = true;
       m = false;
     }
     bool bo = (boM & bit) != 0 || pr;  // a prune adds backoff
-    int cnt = half_count(m);
+    // getPeers' filter for a graft: topic peers not in the mesh nor in
+    // backoff, not direct
+    auto graftable = [&] { return inTopic && !m && !bo && !dir; };
+    int cnt = grp_count<PAIR>(m);
+    // do we have enough peers?
     if (cnt < d.Dlo) {
-      const bool cand = inTopic && !m && !bo && !dir && S >= 0;
       const uint64_t key = gs_key64(d.seed, GS_SITE_GP_DLO, v, hw, vcol, tt);
-      if (select_k_half(cand, key, d.D - cnt)) {
+      if (grp_select<PAIR>(graftable() && S >= 0, key, d.D - cnt)) {
         gr = true;
         m = true;
       }
-      cnt = half_count(m);
+      cnt = grp_count<PAIR>(m);
     }
-    // too many peers: ranked by value through LDS, one half at a time
-    const int cntA = lane_get(cnt, 0), cntB = lane_get(cnt, 32);
-    for (int hh = 0; hh < 2; ++hh) {
-      if ((hh ? cntB : cntA) <= d.Dhi) continue;
-      const int cnth = hh ? cntB : cntA;
+    // do we have too many peers?  Ranked by value through LDS, one group at a time
+    for (int hh = 0; hh < NG; ++hh) {
+      const int cnth = lane_get(cnt, 32 * hh);
+      if (cnth <= d.Dhi) continue;
       const bool mh = m && h == hh;
       const uint64_t k1 = gs_key64(d.seed, GS_SITE_DHI_SHUFFLE, v, hw, vcol, tt);
       int rank1 = 0;
@@ -1666,25 +1702,23 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
       }
       __syncthreads();
     }
-    cnt = half_count(m);
+    cnt = grp_count<PAIR>(m);
     // do we have enough outbound peers?
     if (cnt >= d.Dlo) {
-      const int outb = half_count(m && ob);
+      const int outb = grp_count<PAIR>(m && ob);
       if (outb < d.Dout) {
-        const bool cand = inTopic && !m && !bo && !dir && ob && S >= 0;
         const uint64_t key = gs_key64(d.seed, GS_SITE_GP_DOUT, v, hw, vcol, tt);
-        if (select_k_half(cand, key, d.Dout - outb)) {
+        if (grp_select<PAIR>(graftable() && ob && S >= 0, key, d.Dout - outb)) {
           gr = true;
           m = true;
         }
-        cnt = half_count(m);
+        cnt = grp_count<PAIR>(m);
       }
     }
-    // opportunistic grafting (median of the memoised mesh scores), one half at a time
+    // opportunistic grafting (median of the memoised mesh scores), one group at a time
     if (oppTick) {
-      const int ca = lane_get(cnt, 0), cb = lane_get(cnt, 32);
-      for (int hh = 0; hh < 2; ++hh) {
-        const int cnth = hh ? cb : ca;
+      for (int hh = 0; hh < NG; ++hh) {
+        const int cnth = lane_get(cnt, 32 * hh);
         if (cnth <= 1) continue;
         const bool mh = m && h == hh;
         int rank = 0;
@@ -1698,16 +1732,16 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
         const unsigned long long ml = __ballot(mh && rank == cnth / 2);
         const double median = lane_getf(S, __ffsll((long long)ml) - 1);
         if (median < d.oppThr) {
-          const bool cand = h == hh && inTopic && !m && !bo && !dir && S > median;
           const uint64_t key = gs_key64(d.seed, GS_SITE_GP_OPPORTUNISTIC, v, hw, vcol, tt);
-          if (select_k_half(cand, key, d.OGP)) {
+          if (grp_select<PAIR>(h == hh && graftable() && S > median, key, d.OGP)) {
             gr = true;
             m = true;
           }
         }
       }
     }
-    // a GRAFT spammer re-GRAFTs the topic peers it is in backoff with
+    // a GRAFT spammer re-GRAFTs the topic peers it is in backoff with, leaving
+    // its own mesh as it is (gossipsub_spam_test.go:449-500)
     if (graftSpam && ticks > 1 && inTopic && !m && bo) {
       if (pr) {
         spamGraft |= bit;  // the backoff just added expires after now
@@ -1724,13 +1758,13 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
     const bool emits = nm > 0 && !noFwd && !ihaveSpam;
     const bool baseE = emits && vm && inTopic && !m && !dir;
     bool cand = false;
-    // and no live score of this pair's candidates needs a refresh: step 2
-    // changes nothing either (the halves' live-score states are equal at a
-    // pair boundary and stay so)
+    // and no live score of this turn's candidates needs a refresh: step 2
+    // changes nothing either (the groups' live-score states are equal at a
+    // turn's boundary and stay so)
     if (fast && !__ballot(baseE && (dirty || (dirtyUp && !(Slive >= d.gossipThr)))))
       cand = baseE && Slive >= d.gossipThr;
     else
-    for (int hh = 0; hh < 2; ++hh) {
+    for (int hh = 0; hh < NG; ++hh) {
       if (h == hh) {
         if (pr) {
           stats_prune(d, e, tt);
@@ -1740,46 +1774,35 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
         dirty = dirty || pr;
         dirtyUp = dirtyUp || gr;
       }
-      unsigned long long dm = __ballot(h == hh && baseE && (dirty || (dirtyUp && !(Slive >= d.gossipThr))));
-      while (dm) {  // rare (a peer pruned earlier in this heartbeat): one edge at a time
-        const int j = __ffsll((long long)dm) - 1;
-        dm &= dm - 1;
-        const double sj = edge_score_wave(d, base + (j & 31), lds);
-        if (lane == j) {
-          Slive = sj;
-          dirty = false;
-          dirtyUp = false;
+      live_refresh(d, h == hh && baseE, base, PAIR ? 31 : 63, Slive, dirty, dirtyUp, lds);
+      if (h == hh) cand = baseE && Slive >= d.gossipThr;
+      if constexpr (PAIR) {  // the other half continues from this half's live-score state
+        const double sx = xor32_f64(Slive);
+        const uint32_t fx = xor32_u32((dirty ? 1u : 0u) | (dirtyUp ? 2u : 0u));
+        if (h != hh) {
+          Slive = sx;
+          dirty = (fx & 1) != 0;
+          dirtyUp = (fx & 2) != 0;
         }
       }
-      if (h == hh) cand = baseE && Slive >= d.gossipThr;
-      // the other half continues from this half's live-score state
-      const double sx = xor32_f64(Slive);
-      const uint32_t fx = xor32_u32((dirty ? 1u : 0u) | (dirtyUp ? 2u : 0u));
-      if (h != hh) {
-        Slive = sx;
-        dirty = (fx & 1) != 0;
-        dirtyUp = (fx & 2) != 0;
-      }
     }
-    // ---- 3. IHAVE peer selection of both topics
+    // ---- 3. IHAVE peer selection of the turn's topics
     const unsigned long long c2 = GS_CLK();
     uint64_t ih = 0;
     if (ihaveSpam) {
       ih = (nm > 0 && !noFwd && vm && inTopic) ? bit : 0;  // every topic peer, any score
     } else if (emits) {
-      const int n = half_count(cand);
-      int target = d.Dlazy;
-      const int factor = (int)(d.GossipFactor * (double)n);
-      if (factor > target) target = factor;
+      const int n = grp_count<PAIR>(cand);
+      const int target = ihave_target(d, n);
       bool sel = cand;
       if (target < n) {
         const uint64_t key = gs_key64(d.seed, GS_SITE_EMIT_PEERS, v, hw, vcol, tt);
-        sel = select_k_half(cand, key, target);
+        sel = grp_select<PAIR>(cand, key, target);
       }
       ih = sel ? bit : 0;
     }
-    // ---- this half's topic bits (a half reads and writes only its own
-    // topics' bits; the halves are merged once, after the loop)
+    // ---- this group's topic bits (with PAIR a half reads and writes only its
+    // own topics' bits; the halves are merged once, after the loop)
     myT |= bit;
     meshl = (meshl & ~bit) | (m ? bit : 0ull);
     if (pr) {
@@ -1792,15 +1815,17 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
     cyEmit += c2 - c1;
     cySel += GS_CLK() - c2;
   }
-  // merge: each half's topics from that half (the rest of meshl is unchanged
-  // in both)
-  const uint64_t otherT = xor32_u64(myT);
-  meshl = (meshl & ~otherT) | (xor32_u64(meshl) & otherT);
-  boM |= xor32_u64(boM) & otherT;
-  toprune |= xor32_u64(toprune);
-  tograft |= xor32_u64(tograft);
-  ihave |= xor32_u64(ihave);
-  spamGraft |= xor32_u64(spamGraft);
+  if constexpr (PAIR) {
+    // merge: each half's topics from that half (the rest of meshl is unchanged
+    // in both)
+    const uint64_t otherT = xor32_u64(myT);
+    meshl = (meshl & ~otherT) | (xor32_u64(meshl) & otherT);
+    boM |= xor32_u64(boM) & otherT;
+    toprune |= xor32_u64(toprune);
+    tograft |= xor32_u64(tograft);
+    ihave |= xor32_u64(ihave);
+    spamGraft |= xor32_u64(spamGraft);
+  }
 }
 
 // ---------------------------------------------------------------- heartbeat
@@ -1809,14 +1834,12 @@ __device__ __forceinline__ void hb_pair(const Dev& d, int v, int64_t base, int d
 // maintenance, sendGraftPrune (outbox), mcache.Shift.  Scores are the
 // heartbeat memo (score1, computed after applyIwantPenalties); emitGossip
 // re-scores peers whose stats changed during this heartbeat (live Score()).
-// PAIR (every node has at most 32 peers): the joined topics are handled two at
-// a time, one per half-wave: lanes 32..63 mirror the edges of lanes 0..31 for
-// the topic loop (mesh maintenance and emitGossip's peer selection of topic
-// t0 + 1 next to t0's), with the live-score bookkeeping of emitGossip kept in
-// the serial topic order (hb_pair below).
+// PAIR (every node has at most 32 peers): lanes 32..63 mirror the edges of
+// lanes 0..31 for the joined-topic loop, which then handles two topics at a
+// time, one per half-wave (hb_topics above).
 template <bool PAIR>
 __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, int64_t now, uint64_t ticks, int cur,
-                                                  int head, int newhead, int allExact) {
+                                                  int head, int newhead) {
   __shared__ int plst[64];
   __shared__ int obs[64];
   __shared__ int posOf[64];
@@ -1880,21 +1903,6 @@ __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, 
   double S = vm ? d.score1[e] : 0.0;
   const uint64_t joined = d.sub[v];
   const bool hbNoPX = vm && S < 0 && (meshl & joined) != 0;  // pruned for its negative score: noPX
-  if (d.scoring && !allExact) {
-    // score1 is exact only where k_score_rows<4> recomputed it; the Dhi
-    // ranking compares scores as values, so the mesh members of a topic that
-    // may exceed Dhi get their exact heartbeat-start score now, before any
-    // stats change in this heartbeat
-    bool needX = false;
-    for (int t = 0; t < d.T; ++t) {
-      const bool mt = valid && ((meshl >> t) & 1) && ((joined >> t) & 1);
-      if (__popcll(__ballot(mt)) > d.Dhi) needX |= mt;
-    }
-    const bool exact = valid && (d.sdirty[e] != 0 || !(d.score0[e] >= 0.0));
-    __syncthreads();  // sgw (read for nmT above) becomes the batch's term table
-    edge_scores_batch(d, base, __ballot(needX && !exact), S, (double*)sgw);
-    if (PAIR) S = __shfl(S, el);  // the upper half mirrors the exact scores
-  }
   GS_STAMPH(2, GS_CLK());
   unsigned long long cyMesh = 0, cyEmit = 0, cySel = 0;  // GS_STAMPS: cycles in mesh maintenance / emitGossip
   double Slive = S;  // live Score(p) for emitGossip
@@ -1906,165 +1914,10 @@ __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, 
   const uint32_t hw = (uint32_t)hop;
   const bool graftSpam = behaves(d, v, GS_BEHAVE_GRAFT_SPAM);
   uint64_t spamGraft = 0;  // GRAFTs without a mesh change (not traced as Graft)
-  if constexpr (PAIR) {
-    hb_pair(d, v, base, deg, vm, e, vcol, hop, now, ticks, head, joined, subvM, S, dir, ob, graftSpam, nmT, meshl, boM,
-            Slive, dirty, dirtyUp, tograft, toprune, ihave, spamGraft, plst, obs, posOf, (double*)sgw, cyMesh, cyEmit,
-            cySel);
-    if (!valid) tograft = toprune = ihave = spamGraft = 0;  // the mirror half is done
-  } else
-  for (int t = 0; t < d.T; ++t) {
-    if (!((joined >> t) & 1)) continue;
-    const unsigned long long c0 = GS_CLK();
-    const uint64_t bit = 1ull << t;
-    const bool inTopic = valid && ((subvM >> t) & 1);
-    bool m = valid && (meshl & bit);
-    // drop all peers with negative score, without PX; a GRAFT spammer first
-    // leaves its whole mesh (gossipsub_spam_test.go:428-446)
-    if (m && (S < 0 || (graftSpam && ticks == 1))) {
-      stats_prune(d, e, t);
-      meshl &= ~bit;
-      add_backoff(d, e, t, now, d.PruneBackoff);
-      boM |= bit;
-      toprune |= bit;
-      dirty = true;
-      m = false;
-    }
-    int cnt = __popcll(__ballot(m));
-    // do we have enough peers?
-    if (cnt < d.Dlo) {
-      const bool bo = (boM & bit) != 0;
-      const bool cand = inTopic && !m && !bo && !dir && S >= 0;
-      const uint64_t key = gs_key64(d.seed, GS_SITE_GP_DLO, v, hw, vcol, t);
-      if (select_k_lds(cand, key, d.D - cnt, (uint64_t*)sterm)) {
-        stats_graft(d, e, t, now);
-        meshl |= bit;
-        tograft |= bit;
-        dirtyUp = true;
-        m = true;
-      }
-      cnt = __popcll(__ballot(m));
-    }
-    // do we have too many peers?
-    if (cnt > d.Dhi) {
-      const uint64_t k1 = gs_key64(d.seed, GS_SITE_DHI_SHUFFLE, v, hw, vcol, t);
-      int rank1 = 0;
-      unsigned long long mm = __ballot(m);
-      while (mm) {
-        const int j = __ffsll((long long)mm) - 1;
-        mm &= mm - 1;
-        const double sj = lane_getf(S, j);
-        const uint64_t kj = lane_get64(k1, j);
-        if (sj > S || (sj == S && (kj < k1 || (kj == k1 && j < lane)))) rank1++;
-      }
-      const bool tail = m && rank1 >= d.Dscore;
-      const uint64_t k2 = gs_key64(d.seed, GS_SITE_DHI_TAIL, v, hw, vcol, t);
-      int rank2 = 0;
-      mm = __ballot(tail);
-      while (mm) {
-        const int j = __ffsll((long long)mm) - 1;
-        mm &= mm - 1;
-        const uint64_t kj = lane_get64(k2, j);
-        if (kj < k2 || (kj == k2 && j < lane)) rank2++;
-      }
-      const int pos = tail ? d.Dscore + rank2 : rank1;
-      if (m) plst[pos] = lane;
-      obs[lane] = ob ? 1 : 0;
-      __syncthreads();
-      if (lane == 0) {
-        // keep D_out outbound peers among the first D (gossipsub.go:1389-1429)
-        int outbound = 0;
-        for (int i = 0; i < d.D; ++i) outbound += obs[plst[i]];
-        if (outbound < d.Dout) {
-          if (outbound > 0) {
-            int ih = outbound;
-            for (int i = 1; i < d.D && ih > 0; ++i) {
-              if (obs[plst[i]]) {
-                const int p = plst[i];
-                for (int j = i; j > 0; --j) plst[j] = plst[j - 1];
-                plst[0] = p;
-                ih--;
-              }
-            }
-          }
-          int ineed = d.Dout - outbound;
-          for (int i = d.D; i < cnt && ineed > 0; ++i) {
-            if (obs[plst[i]]) {
-              const int p = plst[i];
-              for (int j = i; j > 0; --j) plst[j] = plst[j - 1];
-              plst[0] = p;
-              ineed--;
-            }
-          }
-        }
-        for (int i = 0; i < cnt; ++i) posOf[plst[i]] = i;
-      }
-      __syncthreads();
-      if (m && posOf[lane] >= d.D) {
-        stats_prune(d, e, t);
-        meshl &= ~bit;
-        add_backoff(d, e, t, now, d.PruneBackoff);
-        boM |= bit;
-        toprune |= bit;
-        dirty = true;
-        m = false;
-      }
-      __syncthreads();
-      cnt = __popcll(__ballot(m));
-    }
-    // do we have enough outbound peers?
-    if (cnt >= d.Dlo) {
-      const int outb = __popcll(__ballot(m && ob));
-      if (outb < d.Dout) {
-        const bool bo = (boM & bit) != 0;
-        const bool cand = inTopic && !m && !bo && !dir && ob && S >= 0;
-        const uint64_t key = gs_key64(d.seed, GS_SITE_GP_DOUT, v, hw, vcol, t);
-        if (select_k_lds(cand, key, d.Dout - outb, (uint64_t*)sterm)) {
-          stats_graft(d, e, t, now);
-          meshl |= bit;
-          tograft |= bit;
-          dirtyUp = true;
-          m = true;
-        }
-        cnt = __popcll(__ballot(m));
-      }
-    }
-    // opportunistic grafting (median of the memoised mesh scores)
-    if (ticks % d.OGT == 0 && cnt > 1) {
-      int rank = 0;
-      unsigned long long mm = __ballot(m);
-      while (mm) {
-        const int j = __ffsll((long long)mm) - 1;
-        mm &= mm - 1;
-        const double sj = lane_getf(S, j);
-        if (sj < S || (sj == S && j < lane)) rank++;
-      }
-      const unsigned long long ml = __ballot(m && rank == cnt / 2);
-      const double median = lane_getf(S, __ffsll((long long)ml) - 1);
-      if (median < d.oppThr) {
-        const bool bo = (boM & bit) != 0;
-        const bool cand = inTopic && !m && !bo && !dir && S > median;
-        const uint64_t key = gs_key64(d.seed, GS_SITE_GP_OPPORTUNISTIC, v, hw, vcol, t);
-        if (select_k_lds(cand, key, d.OGP, (uint64_t*)sterm)) {
-          stats_graft(d, e, t, now);
-          meshl |= bit;
-          tograft |= bit;
-          dirtyUp = true;
-          m = true;
-        }
-      }
-    }
-    // a GRAFT spammer re-GRAFTs the topic peers it is in backoff with, leaving
-    // its own mesh as it is (gossipsub_spam_test.go:449-500)
-    if (graftSpam && ticks > 1 && inTopic && !m && (boM & bit)) {
-      const int64_t be = d.backoff[tix(d, t, e)];
-      if (be != 0 && be > now) spamGraft |= bit;
-    }
-    const unsigned long long c1 = GS_CLK();
-    ihave |= emit_gossip(d, v, t, hop, head, valid, vcol, inTopic, m, dir, Slive, dirty, dirtyUp, base, (double*)sgw,
-                         lane_get(nmT, t));
-    cyMesh += c1 - c0;
-    cyEmit += GS_CLK() - c1;
-  }
+  hb_topics<PAIR>(d, v, base, vm, e, vcol, hop, now, ticks, joined, subvM, S, dir, ob, graftSpam, nmT, meshl, boM, Slive,
+                  dirty, dirtyUp, tograft, toprune, ihave, spamGraft, plst, obs, posOf, (double*)sgw, cyMesh, cyEmit,
+                  cySel);
+  if (PAIR && !valid) tograft = toprune = ihave = spamGraft = 0;  // the mirror half is done
   if (d.doPX) {
     // makePrune with PX for every PRUNE of this heartbeat (sendGraftPrune,
     // gossipsub.go:1636-1647), with the live scores after every mesh change;
@@ -2088,7 +1941,7 @@ __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, 
   GS_STAMPH(3, GS_CLK());
   GS_STAMPH(6, cyMesh);
   GS_STAMPH(7, cyEmit);
-  GS_STAMPH(4, cySel);  // PAIR: the selection part of cyEmit
+  GS_STAMPH(4, cySel);  // step 3 of hb_topics (cyEmit: step 2)
   // expire fanout for topics we haven't published to in a while
   uint64_t fpres = d.fanoutPresent[v];
   {
@@ -2113,12 +1966,12 @@ __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, 
     if (cnt < d.D) {
       const bool cand = inTopic && mc && !f && !dir && S >= d.publishThr;
       const uint64_t key = gs_key64(d.seed, GS_SITE_GP_FANOUT_HB, v, hw, vcol, t);
-      if (select_k_lds(cand, key, d.D - cnt, (uint64_t*)sterm)) {
+      if (select_k(cand, key, d.D - cnt)) {
         fanl |= bit;
         f = true;
       }
     }
-    ihave |= emit_gossip(d, v, t, hop, head, valid, vcol, inTopic && mc, f, dir, Slive, dirty, dirtyUp, base,
+    ihave |= emit_gossip(d, v, t, hop, valid, vcol, inTopic && mc, f, dir, Slive, dirty, dirtyUp, base,
                          (double*)sgw, lane_get(nmT, t));
   }
   // sendGraftPrune + flush: one heartbeat RPC per peer with any control

@@ -1206,7 +1206,7 @@ P6_LIGHT = dict(ip_groups=4, ip_threshold=2, ip_weight=-0.05)   # P6 of the size
 
 def p6_churn(lib, n=120, k=16, topics=1, seed=111, msgs=300, hb=12, ip_groups=5, ip_threshold=3, ip_weight=-35.11,
              retain=Second, dormant_frac=0.3, drops=3, whitelist=None, leaves=0, params=None, churn_nodes=None,
-             extra=(), graph=None, authors=()):
+             app_frac=0.0, app=0.0, extra=(), graph=None, authors=()):
     """Eth2 scoring with `ip_groups` IPs drawn over the nodes and P6 of the given
     threshold and weight; RetainScore `retain`.  dormant_frac of the
     connections start down (no record) and come up at a random hop in 12..89;
@@ -1214,7 +1214,8 @@ def p6_churn(lib, n=120, k=16, topics=1, seed=111, msgs=300, hb=12, ip_groups=5,
     (a positive score drops the record at once, any other is retained and
     expires at the first refresh past `retain`); leaves: topics left per 3 hops
     and re-joined 3-29 hops later, as churn_scored does.  whitelist: (net,
-    mask) pairs; churn_nodes: only connections of these nodes change.
+    mask) pairs; churn_nodes: only connections of these nodes change; app_frac
+    of the nodes have the app score `app`.
     e.conn_events lists the connection events as (hop, a, b)."""
     rng = np.random.default_rng(seed)
     n, g = _graph(graph, n, k, seed)
@@ -1231,7 +1232,11 @@ def p6_churn(lib, n=120, k=16, topics=1, seed=111, msgs=300, hb=12, ip_groups=5,
         opts.append(WithGossipSubParams(params))
     if whitelist is not None:
         opts.append(WithIPWhitelist(whitelist))
-    e = NewGossipSub(n, topics, g, graphs.all_subscribed(n, topics), *opts, *extra, ipv4=ipv4, lib=lib)
+    app_score = None
+    if app_frac:
+        app_score = np.where(np.random.default_rng(seed + 7).random(n) < app_frac, app, 0.0)
+    e = NewGossipSub(n, topics, g, graphs.all_subscribed(n, topics), *opts, *extra, app_score=app_score, ipv4=ipv4,
+                     lib=lib)
     ev = [(int(rng.integers(12, 90)), GS_EV_CONNECT, a, b) for a, b in dormant]
     for h in range(12, hb * 10 - 10, 3):
         for i in rng.choice(len(live), drops, replace=False):
@@ -1351,3 +1356,29 @@ P6 = {
     "ladder_p6_churn": _p6_ladder,
 }
 SCENARIOS.update(P6)
+
+
+# ---------------------------------------------------------------- heartbeat steps
+# Every step of the heartbeat's mesh maintenance in one short run, for each
+# instantiation of the heartbeat kernel's topic loop: degree 40 (one topic per
+# wave) and its twin of degree 32 (two topics per wave, one per half-wave), two
+# topics each.  p6_dhi's shape made smaller, with an opportunistic-graft tick
+# every third heartbeat and an app score of 0.5 on three nodes of ten: a mesh's
+# median stays under OpportunisticGraftThreshold (1) while peers outside it
+# score above the median, so the opportunistic graft, which the other families
+# never reach, takes them.  tests/test_hb_reach.py pins on the oracle that each
+# run holds every step (tests/hb_reach.py); tests/test_hb_reach_gpu.py compares
+# the engine with the oracle after every hop.  Of seeds 131-136 all but 133 reach every
+# step in both runs; 134 has the most heartbeats with each.
+HB_STEPS_SEED = 134
+HB_STEPS_PARAMS = GossipSubParams(OpportunisticGraftTicks=3)
+
+
+def _hb_steps(k):
+    return lambda lib, x=(): p6_churn(lib, n=64, k=k, topics=2, seed=HB_STEPS_SEED, msgs=150, hb=10, ip_groups=4,
+                                      ip_threshold=8, ip_weight=-0.05, params=HB_STEPS_PARAMS, app_frac=0.3, app=0.5,
+                                      extra=x)
+
+
+HB_STEPS = {"hb_steps_40": _hb_steps(40), "hb_steps_32": _hb_steps(32)}
+SCENARIOS.update(HB_STEPS)
