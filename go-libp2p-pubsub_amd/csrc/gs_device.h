@@ -344,6 +344,8 @@ struct Dev {
   double* pad;                 // [256][64][2] scratch targets of branch-free predicated accesses
   unsigned long long* ctr;
   int32_t* err;
+  // latency statistics (gs_latency.h; nullptr: off)
+  uint32_t* latCnt;  // [S] this hop's first deliveries per slot (gs_kernels_lat.h)
 };
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -24,9 +24,11 @@
 #include "../../include/gs_proto.h"
 #include "../../include/gs_rpcsize.h"
 #include "../../include/gs_trace.h"
+#include "../../include/gs_latency.h"
 #include "gs_host.h"
 #include "gs_kernels.h"
 #include "gs_kernels_ctl.h"
+#include "gs_kernels_lat.h"
 #include "gs_exchange.h"
 
 #define HIPCHECK(expr)                                                        \
@@ -358,13 +360,23 @@ struct gs_engine {
   }
   size_t traceOut = 0;
   int drainTrace();
+  // latency statistics (gs_latency.h): the per-message and per-topic tables
+  // ([S][bins] and [T][bins], bins = maxAge + 1; Dev::latCnt holds a hop's
+  // counts) and the grid of k_lat_count
+  bool latOn = false;
+  uint32_t* dLatM = nullptr;
+  unsigned long long* dLatH = nullptr;
+  unsigned latGrid = 0;
+  int latBins() const { return maxAge + 1; }
   // kernel timing: (kernel id, start event, end event) pending until a sync
   bool profiling = false;
   std::vector<hipEvent_t> evPool;
   size_t evUsed = 0;
   std::vector<int> pendKid;
-  double kMs[GS_NUM_KERNELS] = {0};
-  int64_t kLaunches[GS_NUM_KERNELS] = {0};
+  // (past the public kernel ids: the latency kernels, gs_read_latency_kernel_stats)
+  static constexpr int kLatCount = GS_NUM_KERNELS, kLatFold = GS_NUM_KERNELS + 1, kTimed = GS_NUM_KERNELS + 2;
+  double kMs[kTimed] = {0};
+  int64_t kLaunches[kTimed] = {0};
   hipEvent_t nextEvent() {
     if (evUsed == evPool.size()) {
       hipEvent_t ev;
@@ -448,6 +460,8 @@ struct gs_engine {
     stream = nullptr;
     d = Dev{};
     dDev = nullptr;
+    dLatM = nullptr;
+    dLatH = nullptr;
     started = churnOn = allocFailed = false;
     uploaded = 0;
     aliveH.clear();
@@ -514,6 +528,7 @@ struct gs_engine {
   };
   int stepOne(), hopWindow(Hop& hp), fanoutPublish(const Hop& hp), phaseA(const Hop& hp);
   int retireAndPublish(const Hop& hp), phaseB(const Hop& hp);
+  int allocLatency(), latencyStats(const Hop& hp);
   void refreshOrFold(const Hop& hp), heartbeat(const Hop& hp);
   template <bool ADV>
   PhaseADev<ADV> phaseADev() const {

@@ -175,6 +175,7 @@ int gs_engine::buildDevice(const Plan& pl) {
   GS_TRY(allocReadback());
   GS_TRY(allocTrace());
   GS_TRY(allocPartition());
+  GS_TRY(allocLatency());
   GS_TRY(allocFail("state", "; reduce num_nodes or slots_per_topic"));
   GS_TRY(initConnections(pl));
   GS_TRY(allocAcct(pl));
@@ -641,6 +642,23 @@ int gs_engine::allocReadback() {
   return GS_OK;
 }
 
+// Latency statistics (gs_latency.h), at their exact sizes: S + S * bins
+// uint32 and T * bins uint64.
+int gs_engine::allocLatency() {
+  if (!latOn) return GS_OK;
+  const size_t bins = (size_t)latBins();
+  d.latCnt = dalloc<uint32_t>((size_t)S);
+  dLatM = dalloc<uint32_t>((size_t)S * bins);
+  dLatH = dalloc<unsigned long long>((size_t)T * bins);
+  int cus = 0;
+  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
+  // k_lat_count's grid: as many workgroups per CU as its LDS holds of their 4 S byte tables,
+  // GS_LAT_WGS_PER_CU at the most (a workgroup that is not resident only runs as a tail)
+  const unsigned fit = (unsigned)(GS_LAT_CU_LDS / std::max<size_t>((size_t)S * 4, 1));
+  latGrid = std::min<unsigned>(std::max(fit, 1u), GS_LAT_WGS_PER_CU) * (unsigned)std::max(cus, 1);
+  return GS_OK;
+}
+
 int gs_engine::allocTrace() {
   Dev& x = d;
   if (traceMask.empty()) return GS_OK;
@@ -984,6 +1002,7 @@ int gs_engine::stepOne() {
   if (hp.h == 0 && gossip && nOwn()) TIMED(this, GS_K_JOIN, (k_join<<<nOwn(), 64, 0, stream>>>(d, hp.h, hp.now, hp.cur)));
   if (gossip && !floodPublish && hp.n > 0) GS_TRY(fanoutPublish(hp));
   GS_TRY(phaseA(hp));
+  if (latOn) GS_TRY(latencyStats(hp));
   GS_TRY(retireAndPublish(hp));
   // the copies the owned senders send next hop, per edge (phase A reads them)
   if (d.pushOvf) HIPCHECK(hipMemsetAsync(d.pushOvf, 0, 4, stream));
@@ -1116,6 +1135,25 @@ int gs_engine::phaseA(const Hop& hp) {
             k_phase_a<WV, CV(nar), ADV, CV(m) == PA_DENSE>
                 <<<no, 64, lds, stream>>>(phaseADev<ADV>(), h, cur, head, amR, amW, amP, amF, nR, nYp);
         }, wpl_of(W), Pick<4>{mode}, Flag{narrow}));
+  return GS_OK;
+}
+
+// Latency statistics, between phase A and the hop's publishes: the lists and
+// bitmaps hold this hop's first deliveries and no own publish yet.  Nothing
+// is in flight while amR is empty.  Then the per-message rows of the slots
+// this hop's publishes take over are zeroed.
+int gs_engine::latencyStats(const Hop& hp) {
+  const int bins = latBins();
+  const bool inFlight = (hp.amR.m[0] | hp.amR.m[1] | hp.amR.m[2] | hp.amR.m[3]) != 0;
+  if (nOwn() && inFlight) {
+    const int perBlock = denseFlood ? GS_LAT_BLOCK / 64 : GS_LAT_BLOCK / GS_LAT_GROUP;  // nodes in one pass
+    const unsigned grid = std::min(latGrid, nblk(nOwn(), perBlock));
+    TIMED(this, kLatCount, with_consts([&](auto bitmap) {
+            k_lat_count<CV(bitmap)><<<grid, GS_LAT_BLOCK, (size_t)S * 4, stream>>>(d, hp.cur, hp.amR);
+          }, Flag{denseFlood}));
+    TIMED(this, kLatFold, (k_lat_fold<<<nblk(S, 256), 256, 0, stream>>>(d, hp.h, bins, dLatM, dLatH)));
+  }
+  if (hp.n > 0) k_lat_clear<<<hp.n, 64, 0, stream>>>(d, (int)hp.b, bins, dLatM);
   return GS_OK;
 }
 
@@ -2324,6 +2362,78 @@ int gs_read_deliveries(gs_engine* g, int64_t id, int32_t* hop, int32_t* from) {
   return GS_OK;
 }
 
+// ---- latency statistics (include/gs_latency.h)
+int gs_set_latency_stats(gs_engine* g, int32_t on) {
+  if (g->started) { gs_set_error("latency statistics must be set before the first step"); return GS_ESTATE; }
+  g->latOn = on != 0;
+  return GS_OK;
+}
+
+static int latency_ready(const gs_engine* g) {
+  if (!g->latOn) { gs_set_error("latency statistics are off (gs_set_latency_stats)"); return GS_ESTATE; }
+  if (!g->started) { gs_set_error("latency statistics: the engine has not started"); return GS_ESTATE; }
+  return GS_OK;
+}
+
+int gs_latency_bins(const gs_engine* g) {
+  GS_TRY(latency_ready(g));
+  return g->latBins();
+}
+
+static int latency_bins_ok(const gs_engine* g, int32_t bins) {
+  GS_TRY(latency_ready(g));
+  if (bins != g->latBins()) {
+    gs_set_error("latency statistics: bins must be gs_latency_bins() = " + std::to_string(g->latBins()));
+    return GS_EINVAL;
+  }
+  return GS_OK;
+}
+
+int gs_read_latency_hist(gs_engine* g, int64_t* hist, int32_t bins) {
+  GS_TRY(latency_bins_ok(g, bins));
+  HIPCHECK(hipMemcpyAsync(hist, g->dLatH, (size_t)g->T * bins * 8, hipMemcpyDeviceToHost, g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_reset_latency_stats(gs_engine* g) {
+  GS_TRY(latency_ready(g));
+  HIPCHECK(hipMemsetAsync(g->dLatH, 0, (size_t)g->T * g->latBins() * 8, g->stream));
+  return GS_OK;
+}
+
+int gs_read_message_latency(gs_engine* g, int64_t n, const int64_t* ids, uint32_t* hist, int32_t bins) {
+  GS_TRY(latency_bins_ok(g, bins));
+  for (int64_t i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= (int64_t)g->mId.size()) { gs_set_error("unknown message id"); return GS_EINVAL; }
+    if (g->slotOwnerId[g->mSlot[ids[i]]] != ids[i]) {
+      gs_set_error("message slot already recycled (window moved on)");
+      return GS_ESTATE;
+    }
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t* row = hist + i * bins;
+    if (g->mHop[ids[i]] >= g->hop)  // not yet published: its slot may still hold the earlier owner's row
+      std::fill(row, row + bins, 0u);
+    else
+      HIPCHECK(hipMemcpyAsync(row, g->dLatM + (size_t)g->mSlot[ids[i]] * bins, (size_t)bins * 4,
+                              hipMemcpyDeviceToHost, g->stream));
+  }
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_latency_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
+  GS_TRY(latency_ready(g));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  g->resolveTimings();
+  for (int i = 0; i < 2; ++i) {
+    total_ms[i] = g->kMs[gs_engine::kLatCount + i];
+    launches[i] = g->kLaunches[gs_engine::kLatCount + i];
+  }
+  return GS_OK;
+}
+
 #ifdef GS_STAMPS
 // Debug build: phase-A cycle stamps of the sampled nodes of the last hop.
 int gs_debug_stamps(gs_engine* g, unsigned long long* out, int n) {
@@ -2345,7 +2455,7 @@ int gs_set_profiling(gs_engine* g, int on) {
     g->resolveTimings();
   }
   g->profiling = on != 0;
-  for (int i = 0; i < GS_NUM_KERNELS; ++i) { g->kMs[i] = 0; g->kLaunches[i] = 0; }
+  for (int i = 0; i < gs_engine::kTimed; ++i) { g->kMs[i] = 0; g->kLaunches[i] = 0; }
   return GS_OK;
 }
 

@@ -1988,6 +1988,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
   uint8_t* const ffRow = record ? d.ffrom + (int64_t)v * d.S : nullptr;
   const int64_t* const pubHop = d.slotPubHop;
   uint64_t* const pmRow = prow >= 0 ? d.pmask + (int64_t)prow * d.S : nullptr;
+  // latency statistics: a squatter keeps no list for k_lat_count to read, its
+  // first deliveries are counted here (behaviours exist only under ADV)
+  uint32_t* latRow = nullptr;
+  if constexpr (ADV) latRow = noFwd ? d.latCnt : nullptr;
   // randomsub targets (rs_select): a node of degree <= 32 draws two messages'
   // masks per wave step (rs_select2), the odd one last
   const bool rsV = rs_host(d, v);
@@ -2030,6 +2034,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
           else set_err(d, E_FCAP);
         }
         ++rank;
+        if constexpr (ADV)
+          if (latRow != nullptr) atomicAdd(&latRow[slot], 1u);
         if (needAge) ageRow[slot] = (int16_t)(h - ph);
         if (record) ffRow[slot] = (uint8_t)ff;
       };

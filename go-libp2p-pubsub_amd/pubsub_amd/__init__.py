@@ -17,5 +17,5 @@ from .engine import (PRODUCT_LIB, Engine, GossipEngineError, NewFloodSub, NewGos
                      NewRandomSub, PROTOCOLS, WithDevice, WithEventTracer, encode_trace, WithDirectPeers, WithFloodPublish, WithGossipSubParams,
                      WithHop, WithMessageWindow, WithPartition, WithPeerScore, WithPeertxCapacity, WithFrontierLists, WithFrontierBitmaps, WithRecordDeliveries, WithSeed,
                      WithBehaviour, WithPeerGater, WithRPCAccounting, WithValidation, WithPeerExchange, WithDormant,
-                     WithRouters, WithProtocols, WithIPWhitelist,
+                     WithRouters, WithProtocols, WithIPWhitelist, WithLatencyStats, latency_quantiles,
                      load)

@@ -216,6 +216,16 @@ RCCL_FUNCTIONS = [
     ("gs_rccl_destroy", C.c_int, [P]),
 ]
 
+# include/gs_latency.h (product library only; bound by Engine with WithLatencyStats)
+LATENCY_FUNCTIONS = [
+    ("gs_set_latency_stats", C.c_int, [P, i32]),
+    ("gs_latency_bins", C.c_int, [P]),
+    ("gs_read_latency_hist", C.c_int, [P, C.POINTER(i64), i32]),
+    ("gs_reset_latency_stats", C.c_int, [P]),
+    ("gs_read_message_latency", C.c_int, [P, i64, C.POINTER(i64), C.POINTER(u32), i32]),
+    ("gs_read_latency_kernel_stats", C.c_int, [P, C.POINTER(f64), C.POINTER(i64)]),
+]
+
 KERNEL_NAMES = ["score", "refresh", "join", "fanout", "fwd", "phase_a", "publish", "phase_b",
                 "hb_pre", "heartbeat", "push"]
 
