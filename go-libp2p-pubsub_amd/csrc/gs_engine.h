@@ -294,13 +294,13 @@ struct gs_engine {
   // exchange buffers (device) and the pinned host staging of the counts
   DevBuf<uint8_t> xSend{&stream, "exchange buffer"}, xRecv{&stream, "exchange buffer"},
       xSendE{&stream, "exchange buffer"}, xRecvE{&stream, "exchange buffer"};
-  unsigned long long* xCnt = nullptr;  // device: [world] record counts, [world] cursors, bump
-  int64_t* xOff = nullptr;             // device: [world] record offsets
-  unsigned long long* xHost = nullptr; // pinned: world counts, bump, poolCnt, error, push counts [2 world]
+  unsigned long long* xCnt = nullptr;  // device: gsx::XCnt
+  int64_t* xOff = nullptr;             // device: [world] first record per destination (SendPlan::recOff)
+  unsigned long long* xHost = nullptr; // pinned: gsx::Readback
   // cross-rank push (gs_exchange.h k_xp_*): send blocks, device counters
-  // ([world] records, [world] slots, then the same as cursors), block offsets
-  // and record counts ([world] each); a parity's push arena ibx[k] (bytes)
-  // receives them past the owned senders' regions (ibxOwnSlots)
+  // (gsx::XpCnt), k_xp_pack's offsets (gsx::XpOff); a parity's push arena
+  // ibx[k] (bytes) receives the blocks past the owned senders' regions
+  // (ibxOwnSlots)
   DevBuf<uint8_t> xSendP{&stream, "exchange buffer"};
   DevBuf<uint8_t> ibx[2]{{&stream, "exchange buffer"}, {&stream, "exchange buffer"}};
   unsigned long long* xpCnt = nullptr;
@@ -308,7 +308,25 @@ struct gs_engine {
   int64_t ibxOwnSlots = 0;
   double xMs = 0.0;                    // host wall time spent in exchanges
   int64_t xBytes = 0;                  // bytes received by this rank
+  // One hop's exchange (gs_exchange.h, layouts in gs_exchange_wire.h): what its
+  // steps hand on.
+  struct Xchg {
+    int cur;
+    bool hb;
+    bool xpush;          // k_push ran: cross-rank edges' segments travel too
+    bool lists = true;   // the frontier lists travel this hop
+    int64_t nPool = 0;   // arena ids of this rank's segment
+    gsx::Bcast bc{};     // this rank's chunk
+    gsx::SendPlan sp;
+    std::vector<int64_t> all;  // every rank's SizeRow
+    gsx::RecvPlan rp;
+  };
   int exchange(int cur, bool hb);
+  void xPackLists(const Xchg& x);
+  int xCount(Xchg& x), xPackBroadcast(Xchg& x), xPackRecords(Xchg& x), xPackPush(Xchg& x);
+  int xAgreeSizes(Xchg& x);
+  int xGatherChunks(Xchg& x), xGatherDials(Xchg& x), xSwapRecords(Xchg& x), xSwapPush(Xchg& x);
+  int xUnpack(Xchg& x);
   // trace events (gs_set_trace / gs_trace_read)
   std::vector<uint8_t> traceMask;
   int64_t traceCap = 0;

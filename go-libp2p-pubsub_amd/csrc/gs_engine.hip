@@ -690,16 +690,16 @@ int gs_engine::allocPartition() {
   if (world == 1) return GS_OK;
   x.xmark = ealloc<uint8_t>();
   uint8_t* nr = dalloc<uint8_t>(N);
-  xCnt = dalloc<unsigned long long>(2 * world + 1);
+  xCnt = dalloc<unsigned long long>(gsx::XCnt::words(world));
   xOff = dalloc<int64_t>(world);
-  xpCnt = dalloc<unsigned long long>(4 * world);
-  xpOff = dalloc<int64_t>(2 * world);
+  xpCnt = dalloc<unsigned long long>(gsx::XpCnt::words(world));
+  xpOff = dalloc<int64_t>(gsx::XpOff::words(world));
   std::vector<uint8_t> h(N);
   for (int r = 0; r < world; ++r)
     for (int v = part[r]; v < part[r + 1]; ++v) h[v] = (uint8_t)r;
   GS_TRY(putNow(nr, h.data(), (size_t)N));
   x.nodeRank = nr;
-  HIPCHECK(hipHostMalloc((void**)&xHost, (size_t)(3 * world + 4) * 8, hipHostMallocDefault));
+  HIPCHECK(hipHostMalloc((void**)&xHost, gsx::Readback::words(world) * 8, hipHostMallocDefault));
   return GS_OK;
 }
 
@@ -1333,151 +1333,153 @@ int gs_engine::deviceErrorCode(int32_t err) {
   }
 }
 
-static inline size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
+// ---- end-of-hop exchange of a partitioned engine (gs_exchange.h; every layout
+// comes from gs_exchange_wire.h) ----
 
-// End-of-hop exchange of a partitioned engine (gs_exchange.h): pack what this
-// rank's nodes sent in hop h, hand it to the host transport, unpack what the
-// other ranks' nodes sent to ours.
+// End-of-hop exchange: pack what this rank's nodes sent in hop h, hand it to
+// the host transport, unpack what the other ranks' nodes sent to ours.
 int gs_engine::exchange(int cur, bool hb) {
-  const int nOwn = n1 - n0;
-  const size_t hdrBytes = align8((size_t)nOwn * 8);
-  unsigned long long* cnt = xCnt;             // [world]
-  unsigned long long* cursor = xCnt + world;  // [world]
-  unsigned long long* bump = xCnt + 2 * world;
-  // 1. counts + lists (into a buffer that usually suffices; re-packed if not)
-  HIPCHECK(hipMemsetAsync(xCnt, 0, (size_t)(2 * world + 1) * 8, stream));
-  if (eOwn) k_x_count<<<nblk(eOwn, 256), 256, 0, stream>>>(d, cur, cnt);
-  const bool xpush = d.ibxRec[0] != nullptr;  // k_push ran: cross-rank edges' segments travel too
-  if (xpush) {
-    HIPCHECK(hipMemsetAsync(xpCnt, 0, (size_t)4 * world * 8, stream));
-    if (eOwn) k_xp_count<<<nblk(eOwn, 256), 256, 0, stream>>>(d, cur, xpCnt);
-    HIPCHECK(hipMemcpyAsync(xHost + world + 3, xpCnt, (size_t)2 * world * 8, hipMemcpyDeviceToHost, stream));
+  Xchg x{cur, hb, d.ibxRec[0] != nullptr};
+  GS_TRY(xCount(x));
+  GS_TRY(xPackBroadcast(x));
+  // the connector's dials of this hop (peer exchange): every rank applies all
+  // of them at the next hop's start (each launching the sides it owns)
+  x.sp = gsx::planSend(gsx::Readback{xHost, world}, x.xpush, x.bc, x.nPool, hb, x.lists, (int64_t)pxPend.size());
+  GS_TRY(xPackRecords(x));
+  GS_TRY(xPackPush(x));
+  HIPCHECK(hipStreamSynchronize(stream));  // recOff is pageable; the transport reads the buffers
+  const auto t0 = std::chrono::steady_clock::now();
+  GS_TRY(xAgreeSizes(x));
+  GS_TRY(xGatherChunks(x));
+  GS_TRY(xGatherDials(x));
+  GS_TRY(xSwapRecords(x));
+  GS_TRY(xSwapPush(x));
+  xMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return xUnpack(x);
+}
+
+// The owned nodes' frontier lists into xSend: the node header, then the
+// entries that fit (the bump counts on past the capacity).
+void gs_engine::xPackLists(const Xchg& x) {
+  const size_t hdr = gsx::listHeaderBytes(nOwn());
+  const int64_t capEnt = (int64_t)((xSend.cap - hdr) / 4);
+  if (nOwn() && x.lists)
+    k_x_lists<<<nOwn(), 64, 0, stream>>>(d, x.cur, gsx::XCnt{xCnt, world}.bump(), (int64_t*)xSend.p,
+                                         (uint32_t*)(xSend.p + hdr), capEnt);
+}
+
+// Counts per destination and the lists (into a buffer that usually suffices;
+// packed again by xPackBroadcast if not), read back in one host round trip.
+int gs_engine::xCount(Xchg& x) {
+  const int cur = x.cur;
+  const gsx::XCnt cnt{xCnt, world};
+  const gsx::Readback rb{xHost, world};
+  HIPCHECK(hipMemsetAsync(xCnt, 0, gsx::XCnt::words(world) * 8, stream));
+  if (eOwn) k_x_count<<<nblk(eOwn, 256), 256, 0, stream>>>(d, cur, cnt.counts());
+  if (x.xpush) {
+    HIPCHECK(hipMemsetAsync(xpCnt, 0, gsx::XpCnt::words(world) * 8, stream));
+    if (eOwn) k_xp_count<<<nblk(eOwn, 256), 256, 0, stream>>>(d, cur, gsx::XpCnt{xpCnt, world}.counts());
+    HIPCHECK(hipMemcpyAsync(rb.push(), xpCnt, gsx::XpCnt::countWords(world) * 8, hipMemcpyDeviceToHost, stream));
   }
-  GS_TRY(xSend.reserve(hdrBytes + (16u << 20)));
+  GS_TRY(xSend.reserve(gsx::listHeaderBytes(nOwn()) + (16u << 20)));
   // A receiver reads this rank's frontier lists only where it walks them:
   // without push (T < 4), for an IWANT spammer's re-requests, or for a sender
   // whose copies overflowed its push region (record -1).  Otherwise every
-  // cross-rank edge's copies travel as pushed segments (2b below) and the
-  // lists stay home.
+  // cross-rank edge's copies travel as pushed segments and the lists stay home.
   // With push and no IWANT spammers the lists travel only if some sender's
-  // push overflowed: that flag rides in the count readback below (one host
-  // round trip per hop), and the lists are packed after it when needed.
-  bool shipLists = true;
-  const bool deferLists = xpush && d.cSpam[cur] == nullptr;
+  // push overflowed: that flag rides in this readback (one host round trip
+  // per hop), and the lists are packed after it when needed.
+  const bool deferLists = x.xpush && d.cSpam[cur] == nullptr;
   if (deferLists) {
-    xHost[world + 3 + 2 * world] = 0;
-    HIPCHECK(hipMemcpyAsync(&xHost[world + 3 + 2 * world], d.pushOvf, 4, hipMemcpyDeviceToHost, stream));
+    rb.pushOverflow() = 0;
+    HIPCHECK(hipMemcpyAsync(&rb.pushOverflow(), d.pushOvf, 4, hipMemcpyDeviceToHost, stream));
+  } else {
+    xPackLists(x);
   }
-  auto packLists = [&]() {
-    const int64_t capEnt = (int64_t)((xSend.cap - hdrBytes) / 4);
-    if (nOwn && shipLists)
-      k_x_lists<<<nOwn, 64, 0, stream>>>(d, cur, bump, (int64_t*)xSend.p, (uint32_t*)(xSend.p + hdrBytes), capEnt);
-  };
-  if (!deferLists) packLists();
-  HIPCHECK(hipMemcpyAsync(xHost, xCnt, (size_t)world * 8, hipMemcpyDeviceToHost, stream));
-  HIPCHECK(hipMemcpyAsync(xHost + world, bump, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHECK(hipMemcpyAsync(xHost + world + 1, d.poolCnt + (size_t)cur * d.poolSub * 16, 8, hipMemcpyDeviceToHost,
+  HIPCHECK(hipMemcpyAsync(rb.records(), cnt.counts(), (size_t)world * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHECK(hipMemcpyAsync(&rb.entries(), cnt.bump(), 8, hipMemcpyDeviceToHost, stream));
+  HIPCHECK(hipMemcpyAsync(&rb.arenaIds(), d.poolCnt + (size_t)cur * d.poolSub * 16, 8, hipMemcpyDeviceToHost,
                           stream));  // (poolSub == 1 when partitioned)
-  // this rank's device error word travels with the sizes below, so every rank
-  // stops at the same hop (a rank returning alone would leave the others
-  // waiting in the next hop's collectives)
-  xHost[world + 2] = 0;
-  HIPCHECK(hipMemcpyAsync(xHost + world + 2, d.err, 4, hipMemcpyDeviceToHost, stream));
+  // this rank's device error word travels with the sizes (xAgreeSizes), so
+  // every rank stops at the same hop (a rank returning alone would leave the
+  // others waiting in the next hop's collectives)
+  rb.error() = 0;
+  HIPCHECK(hipMemcpyAsync(&rb.error(), d.err, 4, hipMemcpyDeviceToHost, stream));
   HIPCHECK(hipStreamSynchronize(stream));
   if (deferLists) {
-    shipLists = (int32_t)(xHost[world + 3 + 2 * world] & 0xFFFFFFFFu) != 0;
-    if (shipLists) {  // (rare: a sender's copies overflowed its push region)
-      packLists();
-      HIPCHECK(hipMemcpyAsync(xHost + world, bump, 8, hipMemcpyDeviceToHost, stream));
+    x.lists = (int32_t)(rb.pushOverflow() & 0xFFFFFFFFu) != 0;
+    if (x.lists) {  // (rare: a sender's copies overflowed its push region)
+      xPackLists(x);
+      HIPCHECK(hipMemcpyAsync(&rb.entries(), cnt.bump(), 8, hipMemcpyDeviceToHost, stream));
       HIPCHECK(hipStreamSynchronize(stream));
     }
   }
-  const size_t hdrB = shipLists ? hdrBytes : 0;
-  const int32_t myErr = (int32_t)xHost[world + 2];
-  const int64_t nEnt = (int64_t)xHost[world];
-  const int64_t poolBase = (int64_t)rank * poolSeg;
-  const int64_t nPool = std::min<int64_t>((int64_t)xHost[world + 1], poolSeg);
-  const size_t entBytes = align8((size_t)nEnt * 4), poolBytes = align8((size_t)nPool * 4);
-  const size_t gwBytes = hb ? (size_t)nOwn * W * 8 : 0;
+  x.nPool = std::min<int64_t>((int64_t)rb.arenaIds(), poolSeg);
+  return GS_OK;
+}
+
+// This rank's broadcast chunk around the lists already in xSend.  A chunk
+// that outgrew the buffer grows it (which keeps nothing) and packs the lists
+// again.
+int gs_engine::xPackBroadcast(Xchg& x) {
   // randomsub hosts' target masks ride with their list entries (a receiver
   // walking a remote randomsub sender's list filters by them)
-  const size_t selBytes = (shipLists && d.sel != nullptr) ? (size_t)nEnt * 8 : 0;
-  const size_t bcast = hdrB + entBytes + selBytes + poolBytes + gwBytes;
-  if (bcast > xSend.cap) {  // grow (keeps nothing) and pack the lists again
-    GS_TRY(xSend.reserve(bcast));
-    HIPCHECK(hipMemsetAsync(bump, 0, 8, stream));
-    packLists();
+  const gsx::Bcast& b = x.bc = gsx::bcastLayout(nOwn(), (int64_t)gsx::Readback{xHost, world}.entries(), x.nPool, W,
+                                                x.lists, d.sel != nullptr, x.hb);
+  if (b.total > xSend.cap) {
+    GS_TRY(xSend.reserve(b.total));
+    HIPCHECK(hipMemsetAsync(gsx::XCnt{xCnt, world}.bump(), 0, 8, stream));
+    xPackLists(x);
   }
-  if (selBytes && nOwn)
-    k_x_sel<<<nOwn, 64, 0, stream>>>(d, (const int64_t*)xSend.p, (const uint32_t*)(xSend.p + hdrBytes),
-                                     (uint64_t*)(xSend.p + hdrB + entBytes));
-  if (nPool)
-    HIPCHECK(hipMemcpyAsync(xSend.p + hdrB + entBytes + selBytes, d.pool[cur] + poolBase, (size_t)nPool * 4,
+  if (b.masks() && nOwn())
+    k_x_sel<<<nOwn(), 64, 0, stream>>>(d, (const int64_t*)xSend.p, (const uint32_t*)(xSend.p + b.ent),
+                                       (uint64_t*)(xSend.p + b.sel));
+  if (x.nPool)
+    HIPCHECK(hipMemcpyAsync(xSend.p + b.arena, d.pool[x.cur] + (int64_t)rank * poolSeg, (size_t)x.nPool * 4,
                             hipMemcpyDeviceToDevice, stream));
-  if (gwBytes)
-    HIPCHECK(hipMemcpyAsync(xSend.p + hdrB + entBytes + selBytes + poolBytes, d.gw + (size_t)n0 * W, gwBytes,
-                            hipMemcpyDeviceToDevice, stream));
-  // 2. edge records, one block per destination rank
-  std::vector<int64_t> sendRec(world), sendOff(world);
-  int64_t totRec = 0;
-  for (int r = 0; r < world; ++r) {
-    sendRec[r] = (int64_t)xHost[r];
-    sendOff[r] = totRec;
-    totRec += sendRec[r];
+  if (b.gwBytes())
+    HIPCHECK(hipMemcpyAsync(xSend.p + b.gw, d.gw + (size_t)n0 * W, b.gwBytes(), hipMemcpyDeviceToDevice, stream));
+  return GS_OK;
+}
+
+// Edge records, one block per destination rank.
+int gs_engine::xPackRecords(Xchg& x) {
+  GS_TRY(xSendE.reserve((size_t)std::max<int64_t>(x.sp.totRec, 1) * sizeof(XRec)));
+  if (x.sp.totRec) {
+    HIPCHECK(hipMemcpyAsync(xOff, x.sp.recOff.data(), (size_t)world * 8, hipMemcpyHostToDevice, stream));
+    k_x_pack<<<nblk(eOwn, 256), 256, 0, stream>>>(d, x.cur, xOff, gsx::XCnt{xCnt, world}.cursors(), (XRec*)xSendE.p);
   }
-  GS_TRY(xSendE.reserve((size_t)std::max<int64_t>(totRec, 1) * sizeof(XRec)));
-  if (totRec) {
-    HIPCHECK(hipMemcpyAsync(xOff, sendOff.data(), (size_t)world * 8, hipMemcpyHostToDevice, stream));
-    k_x_pack<<<nblk(eOwn, 256), 256, 0, stream>>>(d, cur, xOff, cursor, (XRec*)xSendE.p);
-  }
-  // 2b. pushed segments of cross-rank edges, one block per destination rank:
-  //     [PRec x records][slots]
-  std::vector<int64_t> pRec(world, 0), pSlots(world, 0), pBytes(world, 0), pOff(world, 0);
-  if (xpush) {
-    int64_t tot = 0;
-    for (int r = 0; r < world; ++r) {
-      pRec[r] = (int64_t)xHost[world + 3 + r];
-      pSlots[r] = (int64_t)xHost[world + 3 + world + r];
-      pBytes[r] = 16 * pRec[r] + 2 * pSlots[r];
-      pOff[r] = tot;
-      tot += pBytes[r];
-    }
-    GS_TRY(xSendP.reserve((size_t)std::max<int64_t>(tot, 16)));
-    if (tot) {
-      std::vector<int64_t> offRec(2 * (size_t)world);
-      for (int r = 0; r < world; ++r) {
-        offRec[(size_t)r] = pOff[r];
-        offRec[(size_t)world + r] = pRec[r];
-      }
-      HIPCHECK(hipMemcpyAsync(xpOff, offRec.data(), (size_t)2 * world * 8, hipMemcpyHostToDevice, stream));
-      HIPCHECK(hipMemsetAsync(xpCnt + 2 * world, 0, (size_t)2 * world * 8, stream));
-      k_xp_pack<<<nblk(eOwn, 256), 256, 0, stream>>>(d, cur, xpOff, xpOff + world, xpCnt + 2 * world, xSendP.p);
-    }
-  }
-  HIPCHECK(hipStreamSynchronize(stream));  // sendOff is pageable; the transport reads the buffers
-  // 3. sizes of every rank: [bcast bytes, list entries, arena ids, gw rows?,
-  //    records to rank 0..world-1, device error word, dials, push records to
-  //    rank 0..world-1, push slots to rank 0..world-1]
-  // the connector's dials of this hop (peer exchange): every rank applies all
-  // of them at the next hop's start (each launching the sides it owns)
-  const int nS = 6 + 3 * world;
-  std::vector<int64_t> mine(nS), all((size_t)nS * world);
-  mine[5 + world] = (int64_t)pxPend.size();
-  mine[0] = (int64_t)bcast; mine[1] = nEnt; mine[2] = nPool; mine[3] = (hb ? 1 : 0) | (shipLists ? 2 : 0);
-  for (int r = 0; r < world; ++r) mine[4 + r] = sendRec[r];
-  mine[4 + world] = myErr;
-  for (int r = 0; r < world; ++r) {
-    mine[6 + world + r] = pRec[r];
-    mine[6 + 2 * world + r] = pSlots[r];
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  if (tr.allgather_i64(tr.user, mine.data(), nS, all.data()) != 0) {
+  return GS_OK;
+}
+
+// Pushed segments of cross-rank edges, one block per destination rank.
+int gs_engine::xPackPush(Xchg& x) {
+  if (!x.xpush) return GS_OK;
+  GS_TRY(xSendP.reserve((size_t)std::max<int64_t>(x.sp.pushTotal, 16)));
+  if (!x.sp.pushTotal) return GS_OK;
+  std::vector<int64_t> offRec(gsx::XpOff::words(world));
+  const gsx::XpOff host{offRec.data(), world}, dev{xpOff, world};
+  std::copy(x.sp.pushOff.begin(), x.sp.pushOff.end(), host.blockOff());
+  std::copy(x.sp.pushRec.begin(), x.sp.pushRec.end(), host.records());
+  HIPCHECK(hipMemcpyAsync(xpOff, offRec.data(), offRec.size() * 8, hipMemcpyHostToDevice, stream));
+  unsigned long long* cursors = gsx::XpCnt{xpCnt, world}.cursors();
+  HIPCHECK(hipMemsetAsync(cursors, 0, gsx::XpCnt::countWords(world) * 8, stream));
+  k_xp_pack<<<nblk(eOwn, 256), 256, 0, stream>>>(d, x.cur, dev.blockOff(), dev.records(), cursors, xSendP.p);
+  return GS_OK;
+}
+
+// Every rank's size row; any rank's device error stops every rank here.
+int gs_engine::xAgreeSizes(Xchg& x) {
+  const int nS = gsx::SizeRow::count(world);
+  x.all.resize((size_t)nS * world);
+  if (tr.allgather_i64(tr.user, x.sp.row.data(), nS, x.all.data()) != 0) {
     gs_set_error("transport allgather_i64 failed");
     return GS_EDEVICE;
   }
+  const int32_t myErr = (int32_t)gsx::SizeRow{x.sp.row.data(), world}.error();
   if (myErr) return deviceErrorText(myErr, hop);
   for (int r = 0; r < world; ++r) {
-    const int32_t err = (int32_t)all[(size_t)r * nS + 4 + world];
+    const int32_t err = (int32_t)gsx::SizeRow::of(x.all, world, r).error();
     if (!err) continue;
     const int rc = deviceErrorCode(err);  // the failing rank's code and text
     g_err = "hop " + std::to_string(hop) + ": rank " + std::to_string(r) + ": " + g_err;
@@ -1485,96 +1487,93 @@ int gs_engine::exchange(int cur, bool hb) {
     stickyMsg = g_err;
     return rc;
   }
-  int64_t chunk = 8;
-  for (int r = 0; r < world; ++r) chunk = std::max<int64_t>(chunk, all[(size_t)r * nS]);
-  chunk = (int64_t)align8((size_t)chunk);
-  GS_TRY(xSend.reserve((size_t)chunk, bcast));  // the transport reads `chunk` bytes
-  GS_TRY(xRecv.reserve((size_t)chunk * world));
-  if (tr.allgather(tr.user, xSend.p, xRecv.p, chunk) != 0) {
+  x.rp = gsx::planRecv(x.all, world, rank, x.xpush);
+  return GS_OK;
+}
+
+// All-gather of the broadcast chunks.
+int gs_engine::xGatherChunks(Xchg& x) {
+  GS_TRY(xSend.reserve((size_t)x.rp.chunk, x.bc.total));  // the transport reads `chunk` bytes
+  GS_TRY(xRecv.reserve((size_t)x.rp.chunk * world));
+  if (tr.allgather(tr.user, xSend.p, xRecv.p, x.rp.chunk) != 0) {
     gs_set_error("transport allgather failed");
     return GS_EDEVICE;
   }
-  {
-    int64_t maxD = 0;
-    for (int r = 0; r < world; ++r) maxD = std::max<int64_t>(maxD, all[(size_t)r * nS + 5 + world]);
-    if (maxD > 0) {
-      std::vector<int64_t> dm((size_t)maxD, -1), da((size_t)maxD * world);
-      for (size_t i = 0; i < pxPend.size(); ++i)
-        dm[i] = ((int64_t)pxPend[i].first << 32) | (int64_t)(uint32_t)pxPend[i].second;
-      if (tr.allgather_i64(tr.user, dm.data(), (int32_t)maxD, da.data()) != 0) {
-        gs_set_error("transport allgather_i64 failed (dials)");
-        return GS_EDEVICE;
-      }
-      pxPend.clear();
-      for (int64_t x : da)
-        if (x >= 0) pxPend.push_back({(int)(x >> 32), (int)(uint32_t)x});
-    }
+  return GS_OK;
+}
+
+// Every rank's dials of this hop replace this rank's own in pxPend.
+int gs_engine::xGatherDials(Xchg& x) {
+  const int64_t maxD = x.rp.maxDials;
+  if (maxD <= 0) return GS_OK;
+  const std::vector<int64_t> dm = gsx::packDials(pxPend, maxD);
+  std::vector<int64_t> da((size_t)maxD * world);
+  if (tr.allgather_i64(tr.user, dm.data(), (int32_t)maxD, da.data()) != 0) {
+    gs_set_error("transport allgather_i64 failed (dials)");
+    return GS_EDEVICE;
   }
-  std::vector<int64_t> sendB(world), recvB(world);
-  int64_t totIn = 0;
-  for (int r = 0; r < world; ++r) {
-    sendB[r] = sendRec[r] * (int64_t)sizeof(XRec);
-    recvB[r] = all[(size_t)r * nS + 4 + rank] * (int64_t)sizeof(XRec);
-    totIn += recvB[r];
-  }
-  GS_TRY(xRecvE.reserve((size_t)std::max<int64_t>(totIn, 1)));
-  if (tr.alltoallv(tr.user, xSendE.p, sendB.data(), xRecvE.p, recvB.data()) != 0) {
+  pxPend = gsx::unpackDials(da);
+  return GS_OK;
+}
+
+// All-to-all-v of the edge records.
+int gs_engine::xSwapRecords(Xchg& x) {
+  GS_TRY(xRecvE.reserve((size_t)std::max<int64_t>(x.rp.recTotal, 1)));
+  if (tr.alltoallv(tr.user, xSendE.p, x.sp.recBytes.data(), xRecvE.p, x.rp.recBytes.data()) != 0) {
     gs_set_error("transport alltoallv failed");
     return GS_EDEVICE;
   }
-  // the pushed segments land behind the owned senders' regions of ibx[cur]
-  std::vector<int64_t> pInRec(world, 0), pInOff(world, 0);
-  int64_t pIn = 0;
-  if (xpush) {
-    std::vector<int64_t> pInB(world, 0);
-    for (int r = 0; r < world; ++r) {
-      pInRec[r] = all[(size_t)r * nS + 6 + world + rank];
-      pInB[r] = 16 * pInRec[r] + 2 * all[(size_t)r * nS + 6 + 2 * world + rank];
-      pInOff[r] = pIn;
-      pIn += pInB[r];
-    }
-    const size_t own = (size_t)ibxOwnSlots * 2;
-    // grow this parity's arena where needed, keeping the owned regions (this
-    // hop's segments for local receivers)
-    GS_TRY(ibx[cur].reserve(own + (size_t)pIn, own));
-    d.ibx[cur] = reinterpret_cast<uint16_t*>(ibx[cur].p);
-    if (tr.alltoallv(tr.user, xSendP.p, pBytes.data(), ibx[cur].p + own, pInB.data()) != 0) {
-      gs_set_error("transport alltoallv failed (pushed segments)");
-      return GS_EDEVICE;
-    }
-    xBytes += pIn;
+  return GS_OK;
+}
+
+// All-to-all-v of the push blocks: they land behind the owned senders' regions
+// of ibx[cur].
+int gs_engine::xSwapPush(Xchg& x) {
+  if (!x.xpush) return GS_OK;
+  const int cur = x.cur;
+  const size_t own = (size_t)ibxOwnSlots * 2;
+  // grow this parity's arena where needed, keeping the owned regions (this
+  // hop's segments for local receivers)
+  GS_TRY(ibx[cur].reserve(own + (size_t)x.rp.pushTotal, own));
+  d.ibx[cur] = reinterpret_cast<uint16_t*>(ibx[cur].p);
+  if (tr.alltoallv(tr.user, xSendP.p, x.sp.pushBytes.data(), ibx[cur].p + own, x.rp.pushBytes.data()) != 0) {
+    gs_set_error("transport alltoallv failed (pushed segments)");
+    return GS_EDEVICE;
   }
-  xMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  // 4. unpack the other ranks' parts into the mirrors
+  xBytes += x.rp.pushTotal;
+  return GS_OK;
+}
+
+// The other ranks' parts into the mirrors.
+int gs_engine::xUnpack(Xchg& x) {
+  const int cur = x.cur;
+  const gsx::RecvPlan& rp = x.rp;
   for (int r = 0; r < world; ++r) {
     if (r == rank) continue;
     const int nr = part[r + 1] - part[r];
-    const int64_t* a = &all[(size_t)r * nS];
-    const bool lists = (a[3] & 2) != 0;  // rank r shipped its frontier lists
-    const size_t hB = lists ? align8((size_t)nr * 8) : 0, eB = align8((size_t)a[1] * 4), pB = align8((size_t)a[2] * 4);
-    const size_t sB = (lists && d.sel != nullptr) ? (size_t)a[1] * 8 : 0;  // the entries' randomsub masks
-    const uint8_t* c = xRecv.p + (size_t)r * chunk;
-    xBytes += a[0];
-    if (nr && lists)
-      k_x_unlists<<<nr, 64, 0, stream>>>(d, cur, (const int64_t*)c, (const uint32_t*)(c + hB),
-                                         sB ? (const uint64_t*)(c + hB + eB) : nullptr, part[r]);
-    if (a[2])
-      HIPCHECK(hipMemcpyAsync(d.pool[cur] + (size_t)r * poolSeg, c + hB + eB + sB, (size_t)a[2] * 4,
+    const gsx::SizeRow a = gsx::SizeRow::of(x.all, world, r);
+    const gsx::Bcast b = gsx::bcastLayout(a, nr, W, d.sel != nullptr);
+    const uint8_t* c = xRecv.p + (size_t)r * rp.chunk;
+    xBytes += a.bcastBytes();
+    if (nr && a.lists())
+      k_x_unlists<<<nr, 64, 0, stream>>>(d, cur, (const int64_t*)c, (const uint32_t*)(c + b.ent),
+                                         b.masks() ? (const uint64_t*)(c + b.sel) : nullptr, part[r]);
+    if (a.arenaIds())
+      HIPCHECK(hipMemcpyAsync(d.pool[cur] + (size_t)r * poolSeg, c + b.arena, (size_t)a.arenaIds() * 4,
                               hipMemcpyDeviceToDevice, stream));
-    if ((a[3] & 1) && nr)
-      HIPCHECK(hipMemcpyAsync(d.gw + (size_t)part[r] * W, c + hB + eB + sB + pB, (size_t)nr * W * 8,
-                              hipMemcpyDeviceToDevice, stream));
+    if (a.heartbeat() && nr)
+      HIPCHECK(hipMemcpyAsync(d.gw + (size_t)part[r] * W, c + b.gw, b.gwBytes(), hipMemcpyDeviceToDevice, stream));
   }
-  xBytes += totIn;
-  if (totIn) {
-    const int64_t n = totIn / (int64_t)sizeof(XRec);
+  xBytes += rp.recTotal;
+  if (rp.recTotal) {
+    const int64_t n = rp.recTotal / (int64_t)sizeof(XRec);
     k_x_unpack<<<nblk(n, 256), 256, 0, stream>>>(d, cur, (const XRec*)xRecvE.p, n);
   }
   for (int r = 0; r < world; ++r) {
-    if (!pInRec[r]) continue;
-    const uint8_t* blk = reinterpret_cast<const uint8_t*>(d.ibx[cur]) + (size_t)ibxOwnSlots * 2 + pInOff[r];
-    const int64_t slotBase = ibxOwnSlots + (pInOff[r] + 16 * pInRec[r]) / 2;
-    k_xp_unpack<<<nblk(pInRec[r], 256), 256, 0, stream>>>(d, cur, (const PRec*)blk, pInRec[r], slotBase);
+    if (!rp.pushRec[r]) continue;
+    const uint8_t* blk = reinterpret_cast<const uint8_t*>(d.ibx[cur]) + (size_t)ibxOwnSlots * 2 + rp.pushOff[r];
+    k_xp_unpack<<<nblk(rp.pushRec[r], 256), 256, 0, stream>>>(
+        d, cur, (const PRec*)blk, rp.pushRec[r], gsx::pushSlotBase(ibxOwnSlots, rp.pushOff[r], rp.pushRec[r]));
   }
   HIPCHECK(hipGetLastError());
   return GS_OK;

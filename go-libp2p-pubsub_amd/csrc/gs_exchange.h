@@ -15,18 +15,40 @@
 //   - after a heartbeat, the sender's IHAVE payload row gw[u].
 // Each rank keeps a full-size mirror of these arrays: its own nodes' entries
 // are written by its kernels, every other entry by the unpack kernels below.
-// At the end of hop h the parity written in h is exchanged:
-//   broadcast part (all-gather, equal chunks):
-//     [node header: (off << 16 | len) per owned node][list entries]
-//     [randomsub target masks of the entries, engines with randomsub hosts]
-//     [the rank's arena segment][gw rows of owned nodes, heartbeat hops only]
-//   edge records (all-to-all-v, block per destination rank): one XRec per
-//     owned edge whose receiver lives on another rank and whose forwarding set
-//     changed or whose control outbox is not empty.  Records are moved: the
-//     sender's copy of the outbox entry is cleared once packed (the receiver's
-//     phase B clears its mirror after consuming it, exactly as for local edges).
+// At the end of hop h the parity written in h is exchanged.  The layouts of
+// everything that travels, and of the counter blocks behind it, are stated
+// once in gs_exchange_wire.h (host C++, used by both ends); the kernels below
+// fill and read them.  The sequence of one hop (gs_engine::exchange):
+//   count    k_x_count / k_xp_count / k_x_lists into the device counter blocks
+//            (XCnt, XpCnt), read back with the arena count, the device error
+//            word and the push-overflow flag (Readback);
+//   pack     the broadcast chunk (Bcast):
+//              [node header: (off << 16 | len) per owned node][list entries]
+//              [randomsub target masks of the entries, engines with randomsub hosts]
+//              [the rank's arena segment][gw rows of owned nodes, heartbeat hops only]
+//            with push (below) the header, entries and masks travel only when
+//            a receiver still walks a sender's list;
+//            the edge records, one block per destination rank: one XRec per
+//            owned edge whose receiver lives on another rank and whose
+//            forwarding set changed or whose control outbox is not empty.
+//            Records are moved: the sender's copy of the outbox entry is
+//            cleared once packed (the receiver's phase B clears its mirror
+//            after consuming it, exactly as for local edges);
+//            the push blocks, one per destination rank: [PRec x records][slots];
+//   agree    allgather_i64 of one SizeRow per rank: the sizes of all of the
+//            above, the flags (heartbeat hop, lists shipped), the device error
+//            word (any rank's error stops every rank at this hop) and the
+//            number of peer-exchange dials;
+//   move     all-gather of the chunks (equal size: the largest, 8-aligned),
+//            allgather_i64 of the dials (node pairs, rows padded with -1; only
+//            when some rank has one), all-to-all-v of the edge records,
+//            all-to-all-v of the push blocks (engines that push) straight
+//            behind the owned senders' regions of ibx[cur];
+//   unpack   k_x_unlists / arena and gw copies per source rank (its chunk laid
+//            out from its SizeRow), k_x_unpack, k_xp_unpack per source rank.
 #pragma once
 #include "gs_device.h"
+#include "gs_exchange_wire.h"
 
 struct XRec {  // 96 bytes
   int32_t e;   // the sender's edge (receiver reads it as rev[e'])
@@ -38,7 +60,7 @@ struct XRec {  // 96 bytes
   int64_t spam;  // an IWANT spammer's re-request list (arena record), -1 = none
   int64_t px;    // the PRUNEs' peer-exchange lists (arena record), -1 = none
 };
-static_assert(sizeof(XRec) == 96, "XRec layout");
+static_assert(sizeof(XRec) == 96 && sizeof(XRec) == gsx::kXRecBytes, "XRec layout");
 
 __device__ __forceinline__ bool x_needed(const Dev& d, int cur, int64_t e, int& dest) {
   dest = d.nodeRank[d.col[e]];
@@ -198,7 +220,7 @@ struct PRec {  // 16 bytes
   int32_t n;    // copies, -1 = walk the sender's list
   int64_t off;  // first slot of the segment, in slots from the block's slot region
 };
-static_assert(sizeof(PRec) == 16, "PRec layout");
+static_assert(sizeof(PRec) == 16 && sizeof(PRec) == gsx::kPRecBytes, "PRec layout");
 
 __device__ __forceinline__ bool xp_needed(const Dev& d, int cur, int64_t e, int& dest) {
   dest = d.nodeRank[d.col[e]];
