@@ -25,10 +25,12 @@
 #include "../../include/gs_rpcsize.h"
 #include "../../include/gs_trace.h"
 #include "../../include/gs_latency.h"
+#include "../../include/gs_inspect.h"
 #include "gs_host.h"
 #include "gs_kernels.h"
 #include "gs_kernels_ctl.h"
 #include "gs_kernels_lat.h"
+#include "gs_kernels_insp.h"
 #include "gs_exchange.h"
 
 #define HIPCHECK(expr)                                                        \
@@ -386,13 +388,31 @@ struct gs_engine {
   unsigned long long* dLatH = nullptr;
   unsigned latGrid = 0;
   int latBins() const { return maxAge + 1; }
+  // WithPeerScoreInspect (gs_inspect.h): a ring of inspCap ticks, each a row
+  // (insp_row_len: score_hist, then mesh_deg), the sampled edges' scores and,
+  // extended, their snapshot fields (k_inspect_gather's layout)
+  bool inspOn = false, inspExt = false;
+  int64_t inspPeriod = 0, inspTaken = 0;
+  int inspCap = 0;
+  std::vector<double> inspBounds;
+  std::vector<uint8_t> inspMask;     // [N] observers, or empty
+  std::vector<int64_t> inspEdges;    // the sampled edges of this rank, ascending
+  unsigned long long* dInspRows = nullptr;
+  double *dInspBounds = nullptr, *dInspScore = nullptr, *dInspExt = nullptr;
+  int64_t* dInspEdges = nullptr;
+  unsigned inspGrid = 0;
+  int inspRowLen() const { return insp_row_len((int)inspBounds.size(), T); }
+  size_t inspExtLen() const { return inspEdges.size() * (3 + 4 * (size_t)T); }  // 8-byte words per tick
   // kernel timing: (kernel id, start event, end event) pending until a sync
   bool profiling = false;
   std::vector<hipEvent_t> evPool;
   size_t evUsed = 0;
   std::vector<int> pendKid;
-  // (past the public kernel ids: the latency kernels, gs_read_latency_kernel_stats)
-  static constexpr int kLatCount = GS_NUM_KERNELS, kLatFold = GS_NUM_KERNELS + 1, kTimed = GS_NUM_KERNELS + 2;
+  // (past the public kernel ids: the latency kernels, gs_read_latency_kernel_stats, and the
+  // inspection's three passes, gs_read_inspect_kernel_stats)
+  static constexpr int kLatCount = GS_NUM_KERNELS, kLatFold = GS_NUM_KERNELS + 1;
+  static constexpr int kInspScore = GS_NUM_KERNELS + 2, kInspReduce = GS_NUM_KERNELS + 3;
+  static constexpr int kInspGather = GS_NUM_KERNELS + 4, kTimed = GS_NUM_KERNELS + 5;
   double kMs[kTimed] = {0};
   int64_t kLaunches[kTimed] = {0};
   hipEvent_t nextEvent() {
@@ -480,6 +500,11 @@ struct gs_engine {
     dDev = nullptr;
     dLatM = nullptr;
     dLatH = nullptr;
+    dInspRows = nullptr;
+    dInspBounds = dInspScore = dInspExt = nullptr;
+    dInspEdges = nullptr;
+    inspEdges.clear();
+    inspTaken = 0;
     started = churnOn = allocFailed = false;
     uploaded = 0;
     aliveH.clear();
@@ -547,6 +572,7 @@ struct gs_engine {
   int stepOne(), hopWindow(Hop& hp), fanoutPublish(const Hop& hp), phaseA(const Hop& hp);
   int retireAndPublish(const Hop& hp), phaseB(const Hop& hp);
   int allocLatency(), latencyStats(const Hop& hp);
+  int allocInspect(), inspectTick();
   void refreshOrFold(const Hop& hp), heartbeat(const Hop& hp);
   template <bool ADV>
   PhaseADev<ADV> phaseADev() const {

@@ -176,6 +176,7 @@ int gs_engine::buildDevice(const Plan& pl) {
   GS_TRY(allocTrace());
   GS_TRY(allocPartition());
   GS_TRY(allocLatency());
+  GS_TRY(allocInspect());
   GS_TRY(allocFail("state", "; reduce num_nodes or slots_per_topic"));
   GS_TRY(initConnections(pl));
   GS_TRY(allocAcct(pl));
@@ -659,6 +660,64 @@ int gs_engine::allocLatency() {
   return GS_OK;
 }
 
+// WithPeerScoreInspect (gs_inspect.h): the sampled edges (the out-edges of the
+// owned observers, ascending), the ring at its exact size and
+// k_inspect_reduce's grid.
+int gs_engine::allocInspect() {
+  if (!inspOn) return GS_OK;
+  inspEdges.clear();
+  if (!inspMask.empty())
+    for (int u = n0; u < n1; ++u)
+      if (inspMask[u])
+        for (int64_t e = rowptr[u]; e < rowptr[u + 1]; ++e) inspEdges.push_back(e);
+  const size_t nS = inspEdges.size(), cap = (size_t)inspCap, nb = inspBounds.size();
+  const bool before = allocFailed;
+  allocFailed = false;
+  dInspRows = dalloc<unsigned long long>(cap * (size_t)inspRowLen());
+  dInspBounds = dalloc<double>(std::max<size_t>(nb, 1));
+  if (nS) {
+    dInspEdges = dalloc<int64_t>(nS);
+    dInspScore = dalloc<double>(cap * nS);
+    if (inspExt) dInspExt = dalloc<double>(cap * inspExtLen());
+  }
+  if (allocFailed) return allocFail("score inspection ring", "; reduce ticks or the sampled nodes");
+  allocFailed = before;
+  GS_TRY(put(dInspBounds, inspBounds.data(), nb));
+  GS_TRY(putNow(dInspEdges, inspEdges.data(), nS));
+  int cus = 0;
+  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
+  // k_inspect_reduce's grid: as many workgroups per CU as its LDS holds of their tables,
+  // GS_INSP_WGS_PER_CU at the most (a workgroup that is not resident only runs as a tail)
+  const unsigned fit = (unsigned)(GS_INSP_CU_LDS / insp_lds_bytes((int)nb, T));
+  inspGrid = std::min<unsigned>(std::max(fit, 1u), GS_INSP_WGS_PER_CU) * (unsigned)std::max(cus, 1);
+  return GS_OK;
+}
+
+// A tick at the end of a hop (`hop` already counts it): the exact scores as
+// gs_read_scores computes them, then the row and the sampled edges into the
+// tick's ring slot.  Nothing is read back: the host knows a tick's hop.
+int gs_engine::inspectTick() {
+  const int slot = (int)(inspTaken % inspCap);
+  const int nb = (int)inspBounds.size();
+  const int64_t nS = (int64_t)inspEdges.size();
+  unsigned long long* row = dInspRows + (size_t)slot * inspRowLen();
+  HIPCHECK(hipMemsetAsync(row, 0, (size_t)inspRowLen() * 8, stream));
+  TIMED(this, kInspScore, (score_rows<0>(d, eOwn, T, dScoreTmp, stream)));
+  if (nOwn()) {
+    const unsigned grid = std::min(inspGrid, nblk(nOwn(), GS_INSP_BLOCK / 64));
+    TIMED(this, kInspReduce, (k_inspect_reduce<<<grid, GS_INSP_BLOCK, insp_row_lds(nb, T), stream>>>(
+                                 d, dScoreTmp, dInspBounds, nb, row)));
+  }
+  if (nS) {
+    double* ext = inspExt ? dInspExt + (size_t)slot * inspExtLen() : nullptr;
+    TIMED(this, kInspGather, (k_inspect_gather<<<nblk(nS * T, 256), 256, 0, stream>>>(
+                                 d, dInspEdges, nS, dScoreTmp, dInspScore + (size_t)slot * nS, ext)));
+  }
+  HIPCHECK(hipGetLastError());
+  inspTaken++;
+  return GS_OK;
+}
+
 int gs_engine::allocTrace() {
   Dev& x = d;
   if (traceMask.empty()) return GS_OK;
@@ -1021,6 +1080,7 @@ int gs_engine::stepOne() {
   HIPCHECK(hipGetLastError());
   if (world > 1) GS_TRY(exchange(hp.cur, heartbeatDue(hp.now)));
   hop++;
+  if (inspOn && hop % inspPeriod == 0) GS_TRY(inspectTick());
   return GS_OK;
 }
 
@@ -2429,6 +2489,130 @@ int gs_read_latency_kernel_stats(gs_engine* g, double* total_ms, int64_t* launch
   for (int i = 0; i < 2; ++i) {
     total_ms[i] = g->kMs[gs_engine::kLatCount + i];
     launches[i] = g->kLaunches[gs_engine::kLatCount + i];
+  }
+  return GS_OK;
+}
+
+// ---- WithPeerScoreInspect (include/gs_inspect.h)
+int gs_set_score_inspect(gs_engine* g, const gs_inspect_config* c) {
+  if (g->started) { gs_set_error("the peer score inspector must be set before the first step"); return GS_ESTATE; }
+  if (g->inspOn) { gs_set_error("duplicate peer score inspector"); return GS_ESTATE; }
+  if (g->cfg.router != GS_ROUTER_GOSSIPSUB) { gs_set_error("pubsub router is not gossipsub"); return GS_EUNSUPPORTED; }
+  if (!g->scoring) { gs_set_error("peer scoring is not enabled"); return GS_EUNSUPPORTED; }
+  if (!c || c->period_hops <= 0) { gs_set_error("score inspection: period_hops must be positive"); return GS_EINVAL; }
+  if (c->ticks < 1) { gs_set_error("score inspection: ticks must be at least 1"); return GS_EINVAL; }
+  if (c->num_bounds < 0 || c->num_bounds > GS_INSPECT_MAX_BOUNDS || (c->num_bounds > 0 && !c->bounds)) {
+    gs_set_error("score inspection: num_bounds must be 0.." + std::to_string(GS_INSPECT_MAX_BOUNDS));
+    return GS_EINVAL;
+  }
+  for (int i = 0; i < c->num_bounds; ++i)
+    if (!std::isfinite(c->bounds[i]) || (i > 0 && !(c->bounds[i - 1] < c->bounds[i]))) {
+      gs_set_error("score inspection: bounds must be finite and strictly ascending");
+      return GS_EINVAL;
+    }
+  g->inspPeriod = c->period_hops;
+  g->inspCap = c->ticks;
+  g->inspBounds.assign(c->bounds, c->bounds + c->num_bounds);
+  g->inspMask.clear();
+  if (c->node_mask) g->inspMask.assign(c->node_mask, c->node_mask + g->N);
+  g->inspExt = c->extended != 0;
+  g->inspOn = true;
+  return GS_OK;
+}
+
+static int inspect_on(const gs_engine* g) {
+  if (!g->inspOn) { gs_set_error("score inspection is off (gs_set_score_inspect)"); return GS_ESTATE; }
+  return GS_OK;
+}
+
+// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
+static int inspect_tick_ok(const gs_engine* g, int64_t tick) {
+  GS_TRY(inspect_on(g));
+  if (tick < 0 || tick >= g->inspTaken) {
+    gs_set_error("score inspection: tick " + std::to_string(tick) + " not taken yet (" +
+                 std::to_string(g->inspTaken) + " so far)");
+    return GS_EINVAL;
+  }
+  if (tick < g->inspTaken - g->inspCap) {
+    gs_set_error("score inspection: tick " + std::to_string(tick) + " already overwritten (ring of " +
+                 std::to_string(g->inspCap) + ")");
+    return GS_ESTATE;
+  }
+  return GS_OK;
+}
+
+int64_t gs_inspect_ticks(const gs_engine* g) {
+  GS_TRY(inspect_on(g));
+  return g->inspTaken;
+}
+
+int gs_inspect_num_edges(const gs_engine* g, int64_t* n) {
+  GS_TRY(inspect_on(g));
+  if (!g->started) { gs_set_error("score inspection: the engine has not started"); return GS_ESTATE; }
+  *n = (int64_t)g->inspEdges.size();
+  return GS_OK;
+}
+
+int gs_inspect_edges(gs_engine* g, int64_t* edges, int64_t cap) {
+  int64_t n = 0;
+  GS_TRY(gs_inspect_num_edges(g, &n));
+  if (cap < n || (n > 0 && !edges)) { gs_set_error("score inspection: edge buffer too small"); return GS_EINVAL; }
+  std::copy(g->inspEdges.begin(), g->inspEdges.end(), edges);
+  return GS_OK;
+}
+
+int gs_read_inspect_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* score_hist, int64_t* mesh_deg) {
+  GS_TRY(inspect_tick_ok(g, tick));
+  if (hop) *hop = (tick + 1) * g->inspPeriod;
+  const size_t nh = g->inspBounds.size() + 1;
+  const unsigned long long* row = g->dInspRows + (size_t)(tick % g->inspCap) * g->inspRowLen();
+  if (score_hist) HIPCHECK(hipMemcpyAsync(score_hist, row, nh * 8, hipMemcpyDeviceToHost, g->stream));
+  if (mesh_deg)
+    HIPCHECK(hipMemcpyAsync(mesh_deg, row + nh, (size_t)g->T * GS_INSPECT_DEG_BINS * 8, hipMemcpyDeviceToHost,
+                            g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_inspect_scores(gs_engine* g, int64_t tick, double* score) {
+  GS_TRY(inspect_tick_ok(g, tick));
+  const size_t nS = g->inspEdges.size();
+  if (nS)
+    HIPCHECK(hipMemcpyAsync(score, g->dInspScore + (size_t)(tick % g->inspCap) * nS, nS * 8, hipMemcpyDeviceToHost,
+                            g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_inspect_snapshot(gs_engine* g, int64_t tick, double* app, double* ip_colocation,
+                             double* behaviour_penalty, int64_t* time_in_mesh, double* fmd, double* mmd,
+                             double* imd) {
+  GS_TRY(inspect_tick_ok(g, tick));
+  if (!g->inspExt) { gs_set_error("score inspection: the snapshot fields are not kept (extended = 0)"); return GS_ESTATE; }
+  const size_t nS = g->inspEdges.size(), nk = nS * (size_t)g->T;
+  if (nS) {
+    const double* x = g->dInspExt + (size_t)(tick % g->inspCap) * g->inspExtLen();
+    void* const dst[7] = {app, ip_colocation, behaviour_penalty, time_in_mesh, fmd, mmd, imd};
+    size_t off = 0;
+    for (int f = 0; f < 7; ++f) {
+      const size_t len = f < 3 ? nS : nk;
+      if (dst[f]) HIPCHECK(hipMemcpyAsync(dst[f], x + off, len * 8, hipMemcpyDeviceToHost, g->stream));
+      off += len;
+    }
+  }
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_inspect_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
+  GS_TRY(inspect_on(g));
+  if (g->started) {
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    g->resolveTimings();
+  }
+  for (int i = 0; i < 3; ++i) {
+    total_ms[i] = g->kMs[gs_engine::kInspScore + i];
+    launches[i] = g->kLaunches[gs_engine::kInspScore + i];
   }
   return GS_OK;
 }

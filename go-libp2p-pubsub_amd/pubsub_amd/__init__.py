@@ -18,4 +18,5 @@ from .engine import (PRODUCT_LIB, Engine, GossipEngineError, NewFloodSub, NewGos
                      WithHop, WithMessageWindow, WithPartition, WithPeerScore, WithPeertxCapacity, WithFrontierLists, WithFrontierBitmaps, WithRecordDeliveries, WithSeed,
                      WithBehaviour, WithPeerGater, WithRPCAccounting, WithValidation, WithPeerExchange, WithDormant,
                      WithRouters, WithProtocols, WithIPWhitelist, WithLatencyStats, latency_quantiles,
+                     WithPeerScoreInspect, PeerScoreSnapshot, TopicScoreSnapshot, default_inspect_bounds,
                      load)

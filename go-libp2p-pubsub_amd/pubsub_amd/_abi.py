@@ -226,6 +226,32 @@ LATENCY_FUNCTIONS = [
     ("gs_read_latency_kernel_stats", C.c_int, [P, C.POINTER(f64), C.POINTER(i64)]),
 ]
 
+# include/gs_inspect.h (product library only; bound by Engine with WithPeerScoreInspect)
+GS_INSPECT_MAX_BOUNDS = 63
+GS_INSPECT_DEG_BINS = 65  # mesh degree 0..64
+
+
+class InspectConfigC(C.Structure):
+    _fields_ = [
+        ("period_hops", i64), ("ticks", i32), ("num_bounds", i32), ("bounds", C.POINTER(f64)),
+        ("node_mask", C.POINTER(u8)), ("extended", i32),
+    ]
+
+
+INSPECT_FUNCTIONS = [
+    ("gs_set_score_inspect", C.c_int, [P, C.POINTER(InspectConfigC)]),
+    ("gs_inspect_ticks", i64, [P]),
+    ("gs_inspect_num_edges", C.c_int, [P, C.POINTER(i64)]),
+    ("gs_inspect_edges", C.c_int, [P, C.POINTER(i64), i64]),
+    ("gs_read_inspect_row", C.c_int, [P, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    ("gs_read_inspect_scores", C.c_int, [P, i64, C.POINTER(f64)]),
+    ("gs_read_inspect_snapshot", C.c_int,
+     [P, i64, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(i64), C.POINTER(f64), C.POINTER(f64),
+      C.POINTER(f64)]),
+    ("gs_read_inspect_kernel_stats", C.c_int, [P, C.POINTER(f64), C.POINTER(i64)]),
+]
+INSPECT_KERNEL_NAMES = ["insp_score", "insp_reduce", "insp_gather"]
+
 KERNEL_NAMES = ["score", "refresh", "join", "fanout", "fwd", "phase_a", "publish", "phase_b",
                 "hb_pre", "heartbeat", "push"]
 

@@ -14,6 +14,7 @@ explicit `lib=` to drive the CPU oracle through the identical ABI.
 """
 import ctypes as C
 import os
+from dataclasses import dataclass, field
 from fractions import Fraction
 
 import numpy as np
@@ -211,6 +212,74 @@ def latency_quantiles(hist, qs):
     return out
 
 
+@dataclass
+class TopicScoreSnapshot:
+    """score.go:137-142."""
+    TimeInMesh: int = 0
+    FirstMessageDeliveries: float = 0.0
+    MeshMessageDeliveries: float = 0.0
+    InvalidMessageDeliveries: float = 0.0
+
+
+@dataclass
+class PeerScoreSnapshot:
+    """score.go:128-135; Topics is keyed by topic index."""
+    Score: float = 0.0
+    Topics: dict = field(default_factory=dict)
+    AppSpecificScore: float = 0.0
+    IPColocationFactor: float = 0.0
+    BehaviourPenalty: float = 0.0
+
+
+def default_inspect_bounds(thresholds):
+    """WithPeerScoreInspect's default bin bounds: the sorted distinct values of
+    the Graylist-, Publish-, Gossip- and OpportunisticGraftThreshold, 0 and the
+    smallest positive subnormal (so that "exactly 0" has a bin of its own)."""
+    return sorted({float(thresholds.GraylistThreshold), float(thresholds.PublishThreshold),
+                   float(thresholds.GossipThreshold), 0.0, 5e-324,
+                   float(thresholds.OpportunisticGraftThreshold)})
+
+
+def _checked_bounds(bounds):
+    b = np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1)
+    if len(b) > _abi.GS_INSPECT_MAX_BOUNDS:
+        raise ValueError(f"WithPeerScoreInspect: at most {_abi.GS_INSPECT_MAX_BOUNDS} bounds, got {len(b)}")
+    if not np.isfinite(b).all() or not (np.diff(b) > 0).all():
+        raise ValueError("WithPeerScoreInspect: bounds must be finite and strictly ascending")
+    return b
+
+
+def WithPeerScoreInspect(inspect, period, *, bounds=None, nodes=None, ticks=64, extended=False):
+    """WithPeerScoreInspect / WithPeerScoreInspectExtended (score.go:120-175,
+    438-491), taken on the device (include/gs_inspect.h, product library
+    only).  Every `period` (ns, a positive multiple of the hop) the engine
+    keeps, inside step() and without a synchronise, a histogram of all scores
+    over `bounds` (default: default_inspect_bounds of the thresholds), the
+    mesh-degree distribution per topic, and the scores of the peers of the
+    observers in `nodes` (indices or a bool mask) -- with extended=True their
+    PeerScoreSnapshot fields too -- in a ring of `ticks` ticks.  `inspect` is
+    None or a callable: step() then runs in chunks of at most ticks x period
+    and calls inspect(hop, scores) once per tick, in order, with scores =
+    {observer: {peer: score}} (PeerScoreInspectFn) or, extended,
+    {observer: {peer: PeerScoreSnapshot}}.  Read with Engine.inspect_row(),
+    inspect_scores(), inspect_snapshot()."""
+    if inspect is not None and not callable(inspect):
+        raise ValueError("WithPeerScoreInspect: inspect must be None or a callable")
+    if int(ticks) < 1:
+        raise ValueError("WithPeerScoreInspect: ticks must be at least 1")
+    if bounds is not None:
+        bounds = _checked_bounds(bounds)
+    return ("score_inspect", dict(inspect=inspect, period=int(period), bounds=bounds, nodes=nodes, ticks=int(ticks),
+                                  extended=bool(extended)))
+
+
+def _inspect_period_hops(period, hop_ns):
+    if period <= 0 or period % hop_ns:
+        raise ValueError(f"WithPeerScoreInspect: period {period} ns must be a positive multiple of the hop "
+                         f"({hop_ns} ns)")
+    return period // hop_ns
+
+
 def WithPartition(rank, world, transport):
     """Simulate only this rank's node range; exchange RPCs with the other
     ranks through `transport` (a pubsub_amd.transport.TorchTransport) once per
@@ -235,6 +304,9 @@ class Engine:
         cfg.slots_per_topic = opts.get("slots_per_topic", 1024)
         cfg.seed = opts.get("seed", 1)
         cfg.hop_ns = opts.get("hop_ns", 100 * Millisecond)
+        insp = opts.get("score_inspect")
+        if insp is not None:  # refused before anything is created
+            insp = dict(insp, period_hops=_inspect_period_hops(insp["period"], cfg.hop_ns))
         flags = 0
         if score is not None:
             flags |= _abi.GS_FLAG_SCORING
@@ -311,6 +383,29 @@ class Engine:
             if not self._has_latency:
                 self.close()
             _check(self.lib, self._latency_lib().gs_set_latency_stats(h, 1))
+        # include/gs_inspect.h: exported by the product library only
+        self._has_inspect = all(hasattr(self.lib, name) for name, _, _ in _abi.INSPECT_FUNCTIONS)
+        if self._has_inspect:
+            for name, res, args in _abi.INSPECT_FUNCTIONS:
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = res, args
+        self._inspect = None
+        if insp is not None:
+            if not self._has_inspect:
+                self.close()
+            lib = self._inspect_lib()
+            bounds = insp["bounds"]
+            if bounds is None:
+                bounds = _checked_bounds(default_inspect_bounds(score[1])) if score is not None else np.zeros(0)
+            mask = None
+            if insp["nodes"] is not None:
+                mask = np.zeros(num_nodes, dtype=np.uint8)
+                nodes = np.asarray(insp["nodes"])
+                mask[np.nonzero(nodes)[0] if nodes.dtype == bool else nodes.astype(np.int64)] = 1
+            ic = _abi.InspectConfigC(insp["period_hops"], insp["ticks"], len(bounds), _ptr(bounds, C.c_double),
+                                     _ptr(mask, C.c_uint8), 1 if insp["extended"] else 0)
+            _check(lib, lib.gs_set_score_inspect(h, C.byref(ic)))
+            self._inspect = dict(insp, bounds=bounds, mask=mask, delivered=0)
         acct = opts.get("rpc_acct")
         if acct is not None:
             ms, idl, tl, pid, rec = acct
@@ -407,7 +502,17 @@ class Engine:
         return bool(self.lib.gs_frontier_dense(self.h))
 
     def step(self, hops=1):
-        _check(self.lib, self.lib.gs_step(self.h, int(hops)))
+        hops = int(hops)
+        if self._inspect is None or self._inspect["inspect"] is None:
+            _check(self.lib, self.lib.gs_step(self.h, hops))
+            return
+        # a callback: chunks no longer than the ring, so that no tick is overwritten unread
+        chunk = self._inspect["ticks"] * self._inspect["period_hops"]
+        while hops > 0:
+            n = min(hops, chunk)
+            _check(self.lib, self.lib.gs_step(self.h, n))
+            hops -= n
+            self._deliver_ticks()
 
     def sync(self):
         _check(self.lib, self.lib.gs_sync(self.h))
@@ -567,6 +672,103 @@ class Engine:
         _check(self._latency_lib(), self.lib.gs_read_latency_kernel_stats(self.h, _ptr(ms, C.c_double),
                                                                           _ptr(cnt, C.c_int64)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(("lat_count", "lat_fold"))}
+
+    # ---------------------------------------------------------------- score inspection
+    def _inspect_lib(self):
+        if not self._has_inspect:
+            raise ValueError("score inspection (WithPeerScoreInspect): product library only")
+        return self.lib
+
+    def inspect_ticks(self):
+        """Ticks taken so far (gs_inspect_ticks)."""
+        lib = self._inspect_lib()
+        n = lib.gs_inspect_ticks(self.h)
+        if n < 0:
+            _check(lib, int(n))
+        return int(n)
+
+    def inspect_row(self, k):
+        """Tick k: dict(hop, score_hist int64 [len(bounds) + 1], mesh_deg int64
+        [T, 65]) of this rank's owned edges and nodes (gs_read_inspect_row)."""
+        lib = self._inspect_lib()
+        nb = len(self._inspect["bounds"]) if self._inspect else 0
+        hop = C.c_int64()
+        hist = np.zeros(nb + 1, dtype=np.int64)
+        deg = np.zeros((self.T, _abi.GS_INSPECT_DEG_BINS), dtype=np.int64)
+        _check(lib, lib.gs_read_inspect_row(self.h, int(k), C.byref(hop), _ptr(hist, C.c_int64),
+                                            _ptr(deg, C.c_int64)))
+        return dict(hop=hop.value, score_hist=hist, mesh_deg=deg)
+
+    def inspect_edges(self):
+        """The sampled edges of this rank (the out-edges of its observers), ascending."""
+        lib = self._inspect_lib()
+        n = C.c_int64()
+        _check(lib, lib.gs_inspect_num_edges(self.h, C.byref(n)))
+        edges = np.zeros(n.value, dtype=np.int64)
+        _check(lib, lib.gs_inspect_edges(self.h, _ptr(edges, C.c_int64), n.value))
+        return edges
+
+    def inspect_scores(self, k):
+        """The sampled edges' scores at tick k, float64 [len(inspect_edges())]."""
+        lib = self._inspect_lib()
+        n = C.c_int64()
+        _check(lib, lib.gs_inspect_num_edges(self.h, C.byref(n)))
+        a = np.zeros(n.value, dtype=np.float64)
+        _check(lib, lib.gs_read_inspect_scores(self.h, int(k), _ptr(a, C.c_double)))
+        return a
+
+    def inspect_snapshot(self, k):
+        """The sampled edges' PeerScoreSnapshot fields at tick k (extended=True):
+        dict(app, ip_colocation, behaviour_penalty [nS]; time_in_mesh int64, fmd,
+        mmd, imd [nS, T])."""
+        lib = self._inspect_lib()
+        n = C.c_int64()
+        _check(lib, lib.gs_inspect_num_edges(self.h, C.byref(n)))
+        nS, sh = n.value, (n.value, self.T)
+        app, ipc, bp = (np.zeros(nS, dtype=np.float64) for _ in range(3))
+        tim = np.zeros(sh, dtype=np.int64)
+        fmd, mmd, imd = (np.zeros(sh, dtype=np.float64) for _ in range(3))
+        _check(lib, lib.gs_read_inspect_snapshot(self.h, int(k), _ptr(app, C.c_double), _ptr(ipc, C.c_double),
+                                                 _ptr(bp, C.c_double), _ptr(tim, C.c_int64), _ptr(fmd, C.c_double),
+                                                 _ptr(mmd, C.c_double), _ptr(imd, C.c_double)))
+        return dict(app=app, ip_colocation=ipc, behaviour_penalty=bp, time_in_mesh=tim, fmd=fmd, mmd=mmd, imd=imd)
+
+    def inspect_kernel_stats(self):
+        """{"insp_score" | "insp_reduce" | "insp_gather": (total_ms, launches)} since set_profiling(True)."""
+        lib = self._inspect_lib()
+        ms = np.zeros(3, dtype=np.float64)
+        cnt = np.zeros(3, dtype=np.int64)
+        _check(lib, lib.gs_read_inspect_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.INSPECT_KERNEL_NAMES)}
+
+    def _inspect_maps(self, k, edges):
+        """Tick k as the reference's inspect functions get it: {observer: {peer:
+        score}}, or {observer: {peer: PeerScoreSnapshot}} when extended."""
+        obs = np.searchsorted(self.rowptr, edges, side="right") - 1
+        score = self.inspect_scores(k)
+        snap = self.inspect_snapshot(k) if self._inspect["extended"] else None
+        mask, (n0, n1) = self._inspect["mask"], self.node_range
+        out = {int(u): {} for u in (np.flatnonzero(mask[n0:n1]) + n0 if mask is not None else ())}
+        for i, (u, e) in enumerate(zip(obs.tolist(), edges.tolist())):
+            if snap is None:
+                val = float(score[i])
+            else:
+                topics = {t: TopicScoreSnapshot(int(snap["time_in_mesh"][i, t]), float(snap["fmd"][i, t]),
+                                                float(snap["mmd"][i, t]), float(snap["imd"][i, t]))
+                          for t in range(self.T)}
+                val = PeerScoreSnapshot(float(score[i]), topics, float(snap["app"][i]),
+                                        float(snap["ip_colocation"][i]), float(snap["behaviour_penalty"][i]))
+            out.setdefault(u, {})[int(self.col[e])] = val
+        return out
+
+    def _deliver_ticks(self):
+        st = self._inspect
+        taken = self.inspect_ticks()
+        edges = self.inspect_edges() if taken > st["delivered"] else None
+        while st["delivered"] < taken:
+            k = st["delivered"]
+            st["delivered"] += 1
+            st["inspect"]((k + 1) * st["period_hops"], self._inspect_maps(k, edges))
 
     def deliveries(self, msg_id):
         hop = np.empty(self.N, dtype=np.int32)
