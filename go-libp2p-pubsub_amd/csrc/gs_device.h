@@ -1,7 +1,10 @@
 // gs_device.h — device-side state and helpers of the MI355X gossip engine.
 //
-// Layout: message slots are topic-segmented, slot s belongs to
-// topic s / St; a node bitset is W = T*Wt 64-bit words.  Per-node arrays are
+// Layout: message slots are topic-segmented: topic t owns the
+// ring of slots [64 * w0[t], 64 * w0[t + 1]), whole 64-bit words, w0 a prefix
+// table (gs_window_layout.h; gs_window.h sizes each ring).  With every ring the
+// same size St (the default) slot s belongs to topic s / St and the tables are
+// not allocated.  A node bitset is W = w0[T] words.  Per-node arrays are
 // row-major [node][word]; per-edge arrays are indexed by the CSR edge id e
 // (observer u = edge_src[e], neighbour col[e]); per-(edge,topic) state
 // (score counters, backoff) is tiled [e/64][t][e%64] (tix): a wave of 64
@@ -194,7 +197,11 @@ struct Dev {
   int32_t* fex[2]; // [E]
   int32_t* fbN[2]; // [N] bits in the fb row (0: the row is all zero and is not read)
   uint64_t* own;   // [N][W] the live messages the node authored
-  uint32_t stMagic; // ceil(2^32 / St): topic of slot s = umulhi(s, stMagic) (s < 2^16)
+  uint32_t stMagic; // ceil(2^32 / St): topic of slot s = umulhi(s, stMagic) (s < 2^16); 0: wTopic / tW0 below
+  // per-topic windows (gs_window.h; set where stMagic == 0 / nullptr: one age for all):
+  const uint8_t* wTopic;   // [256] topic of word w (words past W: the last topic)
+  const uint16_t* tW0;     // [T + 1] first word of topic t; Wt is then the largest topic's count
+  const int32_t* tAge;     // [T] first-delivery age limit of topic t; maxAge is then the largest
   uint64_t tDivM;   // ceil(2^64 / T) (0 when T == 1): edge of pair p = umul64hi(p, tDivM)
   int32_t maxDeg;  // largest node degree (<= 64)
   uint64_t* oldm;  // [W] slots whose message is too old to be first-delivered this hop
@@ -205,6 +212,7 @@ struct Dev {
   // ---- adversarial model (gs_publish_ex / gs_set_validation / gs_set_behaviour / gater)
   uint8_t* slotKind;     // [S] GS_MSG_* of the slot's message
   uint64_t topicVal;     // topics with a validator (RegisterTopicValidator)
+  uint64_t valW[4];      // the words of those topics' slots (val_word)
   int32_t valQueue;      // validation-queue entries per node per hop, 0 = unlimited
   int32_t anyBehave;     // some node has a GS_BEHAVE_* bit
   const uint8_t* behave; // [N] GS_BEHAVE_* bits (nullptr: all honest)
@@ -349,6 +357,18 @@ struct Dev {
 };
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+// ---- topic windows: the topic of a slot, a topic's first word (t = T: the
+// end of the last), its age limit.  Uniform windows keep the multiply; stMagic
+// == 0 marks the table layout (a flag the multiply loads anyway: the node-wave
+// kernels have no scalar register to spare for a pointer test).
+__device__ __forceinline__ int slot_topic(const Dev& d, int slot) {
+  if (__builtin_expect(d.stMagic == 0u, 0)) return (int)d.wTopic[slot >> 6];
+  return (int)__umulhi((unsigned)slot, d.stMagic);
+}
+// word w holds slots of a topic with a validator (w < 256)
+__device__ __forceinline__ bool val_word(const Dev& d, int w) { return (d.valW[w >> 6] >> (w & 63)) & 1; }
+__device__ __forceinline__ int topic_w0(const Dev& d, int t) { return d.stMagic == 0u ? (int)d.tW0[t] : t * d.Wt; }
+__device__ __forceinline__ int topic_age(const Dev& d, int t) { return d.tAge != nullptr ? d.tAge[t] : d.maxAge; }
 // ---- mixed networks (gossip_engine.h gs_set_routers / gs_set_graph_ex)
 __device__ __forceinline__ int router_of(const Dev& d, int u) { return d.nrouter ? (int)d.nrouter[u] : d.router; }
 __device__ __forceinline__ bool gossip_host(const Dev& d, int u) { return router_of(d, u) == GS_ROUTER_GOSSIPSUB; }

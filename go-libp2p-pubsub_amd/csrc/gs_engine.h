@@ -26,6 +26,8 @@
 #include "../../include/gs_trace.h"
 #include "../../include/gs_latency.h"
 #include "../../include/gs_inspect.h"
+#include "../../include/gs_window.h"
+#include "gs_window_layout.h"
 #include "gs_host.h"
 #include "gs_kernels.h"
 #include "gs_kernels_ctl.h"
@@ -111,7 +113,22 @@ struct gs_engine {
   int N = 0, T = 0, St = 0, Wt = 0, W = 0, S = 0, R = 0;
   int64_t E = 0;
   int H = 16;  // hops per heartbeat (or a nominal 16 for floodsub/randomsub)
-  int64_t retireHops = 0;
+  int64_t retireHops = 0;  // the policy's (setWindow); a topic's own: retireOf(t)
+  // topic windows (gs_window.h): the layout (St / Wt: the largest topic's), the
+  // caller's age limits (0: the policy's) and the largest age in force
+  gsw::Layout lay;
+  std::vector<int32_t> userAge;
+  int ageMax = 0;
+  bool windowsSet = false;  // gs_set_topic_windows was called: the publish guard names the topic
+  bool agesSet() const { return std::any_of(userAge.begin(), userAge.end(), [](int32_t a) { return a > 0; }); }
+  int ageOf(int t) const { return userAge[(size_t)t] > 0 ? userAge[(size_t)t] : maxAge; }
+  int64_t retireOf(int t) const {
+    return gsw::retireHops(ageOf(t), cfg.router == GS_ROUTER_GOSSIPSUB, gp.HistoryLength, H);
+  }
+  void setLayout(const gsw::Layout& L) {
+    lay = L;
+    St = L.maxSlots; Wt = L.maxWords(); W = L.W; S = L.S;
+  }
   std::vector<int32_t> topicLive;  // per-topic live message count (phase-A counter width)
   int64_t hopsSinceFold = 0, foldEvery = 1;  // pending-delivery fold cadence (dlt)
   int64_t eOwn = 0;                          // owned edges e1 - e0 (Dev::eOwn)
@@ -120,16 +137,20 @@ struct gs_engine {
   // delivered since then, so the host folds before that bound could pass 255
   bool narrowDlt = false;
   int64_t foldStart = 0;
-  // Does some topic have more than 255 messages published in [lo, hi]?
-  bool topicOver255(int64_t lo, int64_t hi) {
-    auto it = std::lower_bound(mHop.begin(), mHop.end(), lo);
+  // Does some topic t have more than 255 messages published in [from - retireOf(t), hi]
+  // (its own retire horizon before `from`)?
+  bool topicOver255(int64_t from, int64_t hi) {
+    int64_t back = 0;
+    for (int t = 0; t < T; ++t) back = std::max(back, retireOf(t));
+    auto it = std::lower_bound(mHop.begin(), mHop.end(), from - back);
     std::fill(topicLive.begin(), topicLive.end(), 0);
     for (size_t k = (size_t)(it - mHop.begin()); k < mHop.size() && mHop[k] <= hi; ++k)
-      if (++topicLive[mTopic[k]] > 255) return true;
+      if (mHop[k] >= from - retireOf(mTopic[k]) && ++topicLive[mTopic[k]] > 255) return true;
     return false;
   }
-  bool narrowFoldDue(int64_t h) { return topicOver255(foldStart - retireHops, h); }
+  bool narrowFoldDue(int64_t h) { return topicOver255(foldStart, h); }
   std::vector<uint64_t> yWord, yTabH;          // phase A young-slot tables (per hop)
+  size_t ldsLimit = 0, ldsStaticA = 0;         // LDS per workgroup of the device; phase A's static share
   int64_t refreshedHop = -1;                 // hop of the last refreshScores (S0 exact after it)
   int maxAge = 0;
   // host graph / attributes
@@ -381,13 +402,13 @@ struct gs_engine {
   size_t traceOut = 0;
   int drainTrace();
   // latency statistics (gs_latency.h): the per-message and per-topic tables
-  // ([S][bins] and [T][bins], bins = maxAge + 1; Dev::latCnt holds a hop's
+  // ([S][bins] and [T][bins], bins = the largest age limit + 1; Dev::latCnt holds a hop's
   // counts) and the grid of k_lat_count
   bool latOn = false;
   uint32_t* dLatM = nullptr;
   unsigned long long* dLatH = nullptr;
   unsigned latGrid = 0;
-  int latBins() const { return maxAge + 1; }
+  int latBins() const { return ageMax + 1; }
   // WithPeerScoreInspect (gs_inspect.h): a ring of inspCap ticks, each a row
   // (insp_row_len: score_hist, then mesh_deg), the sampled edges' scores and,
   // extended, their snapshot fields (k_inspect_gather's layout)
@@ -513,7 +534,7 @@ struct gs_engine {
   ~gs_engine() { release(); }
   bool ageWindowNeeded() const {
     for (int t = 0; t < T; ++t)
-      if (tscored[t] && tps[t].MeshMessageDeliveriesWindow < retireHops * cfg.hop_ns) return true;
+      if (tscored[t] && tps[t].MeshMessageDeliveriesWindow < retireOf(t) * cfg.hop_ns) return true;
     return false;
   }
   bool heartbeatDue(int64_t t) const {
@@ -524,7 +545,8 @@ struct gs_engine {
   bool refreshDue(int64_t t) const { return scoring && t > 0 && t % sp.DecayInterval == 0; }
   // Message-window policy: a message must be first delivered within maxAge
   // hops of its publish (phase A tracks first deliverers for those "young"
-  // slots only), and its slot is recycled only after retireHops.  Honest
+  // slots only), and its slot is recycled only after retireHops.  (A topic
+  // may have an age limit of its own, gs_window.h: ageOf / retireOf.)  Honest
   // runs deliver everything within a few hops (3 heartbeats is ample); with
   // the adversarial model (validation drops, the gater, spam) messages can
   // arrive much later through gossip, so the window then spans the gossip
@@ -535,6 +557,8 @@ struct gs_engine {
     maxAge = (adv ? gp.HistoryLength + gp.HistoryGossip + 3 : 3) * H;
     retireHops = maxAge + (int64_t)(gp.HistoryLength + 2) * H;
     if (cfg.router != GS_ROUTER_GOSSIPSUB) retireHops = maxAge + 2;
+    ageMax = 0;  // (userAge: [T] from creation on)
+    for (int t = 0; t < T; ++t) ageMax = std::max(ageMax, ageOf(t));
   }
 
   // start(): what the host works out before the device is touched (every

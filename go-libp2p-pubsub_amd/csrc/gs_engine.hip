@@ -342,7 +342,7 @@ void gs_engine::setDevScalars(const Plan& pl) {
     const int sq = (int)std::ceil(std::sqrt((double)cfg.randomsub_size));
     x.rsTarget = std::max(6, sq);
   }
-  x.maxAge = maxAge; x.seed = cfg.seed; x.hop_ns = cfg.hop_ns;
+  x.maxAge = ageMax; x.seed = cfg.seed; x.hop_ns = cfg.hop_ns;
   x.n0 = n0; x.n1 = n1; x.e0 = e0; x.e1 = e1; x.eOwn = eOwn; x.rank = rank; x.world = world;
   x.nOwnH = nOwn();
   x.TopicScoreCap = sp.TopicScoreCap; x.AppW = sp.AppSpecificWeight; x.IPW = sp.IPColocationFactorWeight;
@@ -367,13 +367,16 @@ void gs_engine::setDevScalars(const Plan& pl) {
   // that long always credits it (score.go:955)
   x.needAge = (x.record || (scoring && ageWindowNeeded())) ? 1 : 0;
   x.maxDeg = std::max(1, pl.maxdeg);
-  x.stMagic = (uint32_t)(((1ull << 32) + (uint64_t)St - 1) / (uint64_t)St);
+  x.stMagic = lay.uniform ? (uint32_t)(((1ull << 32) + (uint64_t)St - 1) / (uint64_t)St) : 0u;  // 0: the tables
   x.tDivM = T == 1 ? 0 : ~0ull / (uint64_t)T + 1;  // ceil(2^64 / T)
-  foldEvery = std::max<int64_t>(1, 65535 / (2 * (int64_t)St));  // a hop adds at most 2*St per (edge, topic)
+  foldEvery = std::max<int64_t>(1, 65535 / (2 * (int64_t)St));  // a hop adds at most 2*St per (edge, topic): the largest topic's
   x.doPX = doPX ? 1 : 0;
   x.PrunePeers = gp.PrunePeers;
   x.acceptPX = thr.AcceptPXThreshold;
   x.topicVal = topicVal;
+  std::fill(std::begin(x.valW), std::end(x.valW), 0ull);
+  for (int w = 0; w < W; ++w)
+    if ((topicVal >> lay.wTopic[(size_t)w]) & 1) x.valW[w >> 6] |= 1ull << (w & 63);
   x.valQueue = valQueue;
   x.anyImd = topicVal != 0 ? 1 : 0;  // P4 can only come from a validator's rejection
   x.anyBehave = behaveAll != 0;
@@ -471,6 +474,25 @@ int gs_engine::allocNodeTables(const Plan& pl) {
   x.oldm = dalloc<uint64_t>(W);
   x.yTab = dalloc<uint64_t>(2 * (size_t)W);
   x.nAuth = dalloc<int32_t>(N);
+  // topic windows (gs_window.h): the lookup tables only where the rings differ
+  // in size, the ages only where a topic has its own
+  if (!lay.uniform) {
+    uint8_t* wt = dalloc<uint8_t>(gsw::kMaxWords);
+    uint16_t* w0 = dalloc<uint16_t>((size_t)T + 1);
+    GS_TRY(allocFail("topic window tables"));
+    GS_TRY(putNow(wt, lay.wTopic.data(), (size_t)gsw::kMaxWords));
+    GS_TRY(putNow(w0, lay.w0.data(), (size_t)T + 1));
+    x.wTopic = wt;
+    x.tW0 = w0;
+  }
+  if (agesSet()) {
+    int32_t* ta = dalloc<int32_t>(T);
+    GS_TRY(allocFail("topic age limits"));
+    std::vector<int32_t> ah((size_t)T);
+    for (int t = 0; t < T; ++t) ah[(size_t)t] = ageOf(t);
+    GS_TRY(putNow(ta, ah.data(), (size_t)T));
+    x.tAge = ta;
+  }
   if (pl.anyRandom) x.sel = dalloc<uint64_t>((size_t)N * S);
   if (mixed) {
     // the hosts' routers (v1.0 folded into gossipsub) and the connections' protocols
@@ -528,7 +550,7 @@ int gs_engine::allocEdgeState() {
   x.fmd = palloc<double>(); x.mmd = palloc<double>(); x.mfp = palloc<double>(); x.imd = palloc<double>();
   // 16-bit pending counts when a topic's slots (at most St + 1 messages live at
   // one hop) fit a byte and the pairs of an edge pack into whole words
-  narrowDlt = St <= 254 && (T % 2) == 0;
+  narrowDlt = St <= 254 && (T % 2) == 0;  // (St: the largest topic's)
   if (narrowDlt) x.dltN = palloc<uint16_t>();
   else x.dlt = palloc<uint32_t>();
   x.graftTime = palloc<int64_t>(); x.meshTime = palloc<int64_t>(); x.flags = palloc<uint8_t>();
@@ -1086,7 +1108,8 @@ int gs_engine::stepOne() {
 
 // This hop's publishes, the active word windows and phase A's young-slot
 // table: per amR word (by rank) the slot mask, then the number of young slots
-// in the words before it.
+// in the words before it.  A message is young, and its word active, while
+// hop - publish hop <= its topic's age limit: the scan starts at the largest.
 int gs_engine::hopWindow(Hop& hp) {
   const int64_t h = hp.h;
   hp.b = hp.e = nextMsg;
@@ -1098,13 +1121,14 @@ int gs_engine::hopWindow(Hop& hp) {
   auto build = [&](int64_t lo, int64_t hi, WMask& m, bool young) {
     auto it = std::lower_bound(mHop.begin(), mHop.end(), lo);
     for (size_t k = (size_t)(it - mHop.begin()); k < mHop.size() && mHop[k] <= hi; ++k) {
+      if (hi - mHop[k] > ageOf(mTopic[k])) continue;  // past its topic's own age limit
       const int w = mSlot[k] >> 6;
       m.m[w >> 6] |= 1ull << (w & 63);
       if (young) yWord[w] |= 1ull << (mSlot[k] & 63);
     }
   };
-  build(h - 1 - maxAge, h - 1, hp.amR, true);
-  build(h - maxAge, h, hp.amW, false);
+  build(h - 1 - ageMax, h - 1, hp.amR, true);
+  build(h - ageMax, h, hp.amW, false);
   int rk = 0;
   for (int w = 0; w < W; ++w) {
     if (!((hp.amR.m[w >> 6] >> (w & 63)) & 1)) continue;
@@ -1161,7 +1185,7 @@ int gs_engine::phaseA(const Hop& hp) {
   // 8-bit (sender, topic) counters when no topic has more than 255 live
   // message slots: a sender delivers each message at most once per hop
   // (E_DOUBLE), so it cannot deliver more copies of one topic than that
-  const bool narrow = !topicOver255(h - retireHops, h);
+  const bool narrow = !topicOver255(h, h);
   if (narrowDlt && !narrow) {  // St <= 254 bounds a topic's live slots by 255: cannot happen
     gs_set_error("internal: 16-bit pending counts without narrow phase-A counters");
     return GS_EDEVICE;
@@ -1179,6 +1203,24 @@ int gs_engine::phaseA(const Hop& hp) {
   size_t lds = (narrow ? 2 : 4) * nCnt + 16 * (size_t)nR + ((2 * ((size_t)W + nR) + 15) & ~(size_t)15) +
                (size_t)nYp + (hasUnc ? 4 * nCnt : 0);
   if (adv) lds += 4 * nCnt + 4 * 64 * 4 + 8 * 64 + 8 * (size_t)nR;
+  // the young slots grow with the age limits the caller sets (gs_window.h):
+  // refuse here what the device cannot hold instead of failing the launch
+  if (!denseFlood && no) {
+    if (ldsLimit == 0) {
+      int lim = 0;
+      hipFuncAttributes fa{};
+      HIPCHECK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg.device));
+      HIPCHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_phase_a<1, false, false, false>)));
+      ldsLimit = (size_t)lim;
+      ldsStaticA = fa.sharedSizeBytes;  // (the same in every instantiation)
+    }
+    if (lds + ldsStaticA > ldsLimit) {
+      gs_set_error("hop " + std::to_string(h) + ": phase A needs " + std::to_string(lds + ldsStaticA) +
+                   " bytes of LDS per workgroup for " + std::to_string(hp.nY) + " young message slots, the device has " +
+                   std::to_string(ldsLimit) + ": lower max_age_hops or the publish rate");
+      return GS_ECAPACITY;
+    }
+  }
   if (no) GS_TRY(upload(dDev, &d, sizeof(Dev)));
   // denseGossip: the words v's fb row of this parity is written over (this
   // hop's window, and what the row held two hops ago)
@@ -1186,15 +1228,17 @@ int gs_engine::phaseA(const Hop& hp) {
   for (int k = 0; k < GS_MAX_WPL; ++k) amF.m[k] = amR.m[k] | amW.m[k] | amWPar[cur].m[k];
   amWPar[cur] = amW;
   if (!no) return GS_OK;
-  TIMED(this, GS_K_PHASE_A, with_consts([&](auto w, auto m, auto nar) {
+  // (topic windows of different sizes: the instantiations that look a slot's
+  // topic up in d.wTopic; the dense pass 1 has one topic)
+  TIMED(this, GS_K_PHASE_A, with_consts([&](auto w, auto m, auto nar, auto tab) {
           constexpr int WV = CV(w) + 1;
           constexpr bool ADV = CV(m) == PA_ADV;
           if constexpr (CV(m) == PA_FLOOD)  // (no counters: one kernel for either width)
             k_flood_a<WV><<<no, 64, 0, stream>>>(d, h, cur, amR, amW, amP);
           else
-            k_phase_a<WV, CV(nar), ADV, CV(m) == PA_DENSE>
+            k_phase_a<WV, CV(nar), ADV, CV(m) == PA_DENSE, CV(tab) && CV(m) != PA_DENSE>
                 <<<no, 64, lds, stream>>>(phaseADev<ADV>(), h, cur, head, amR, amW, amP, amF, nR, nYp);
-        }, wpl_of(W), Pick<4>{mode}, Flag{narrow}));
+        }, wpl_of(W), Pick<4>{mode}, Flag{narrow}, Flag{!lay.uniform}));
   return GS_OK;
 }
 
@@ -1246,7 +1290,7 @@ int gs_engine::phaseB(const Hop& hp) {
   // item); bit 1: a sender's ids over all topics may (handleIHave's iask
   // cut of its wants).  Both run in either phase-B instantiation.
   int cutMode = 0;
-  const int64_t lo = h - (int64_t)(gp.HistoryGossip + 1) * H - maxAge - 2;
+  const int64_t lo = h - (int64_t)(gp.HistoryGossip + 1) * H - ageMax - 2;  // (the largest age: an upper bound)
   const auto a = std::lower_bound(mHop.begin(), mHop.end(), lo);
   const auto b2 = std::upper_bound(mHop.begin(), mHop.end(), h);
   if ((int64_t)(b2 - a) > (int64_t)gp.MaxIHaveLength) {
@@ -1366,7 +1410,8 @@ int gs_engine::deviceErrorCode(int32_t err) {
                    "by default, 2^20 with IWANT spammers)");
       return GS_ECAPACITY;
     case E_LATE:
-      gs_set_error("a message was first delivered later than the message window allows; raise slots_per_topic");
+      gs_set_error(std::string("a message was first delivered later than the message window allows; raise "
+                               "slots_per_topic") + (windowsSet ? " or its topic's max_age_hops (gs_set_topic_windows)" : ""));
       return GS_ECAPACITY;
     case E_TRUNCATE:
       gs_set_error("the MaxIHaveLength cut table overflowed (more than 64 over-length IHAVE items at a node "
@@ -1760,14 +1805,12 @@ int gs_engine_create(const gs_config* cfg, const gs_gossipsub_params* gsp, const
   }
   g->N = cfg->num_nodes;
   g->T = cfg->num_topics;
-  g->St = cfg->slots_per_topic;
-  g->Wt = g->St / 64;
-  g->W = g->T * g->Wt;
-  g->S = g->T * g->St;
-  if (g->W > 64 * GS_MAX_WPL) {
+  if ((int64_t)g->T * cfg->slots_per_topic > gsw::kMaxSlots) {
     gs_set_error("num_topics * slots_per_topic must be <= 16384 in this build");
     return GS_EUNSUPPORTED;
   }
+  g->setLayout(gsw::uniformLayout(g->T, cfg->slots_per_topic));
+  g->userAge.assign(g->T, 0);
   if (gsp) g->gp = *gsp; else gs_default_gossipsub_params(&g->gp);
   g->scoring = (cfg->flags & GS_FLAG_SCORING) != 0 && cfg->router == GS_ROUTER_GOSSIPSUB;
   g->floodPublish = (cfg->flags & GS_FLAG_FLOOD_PUBLISH) != 0;
@@ -1913,16 +1956,15 @@ int gs_publish_ex(gs_engine* g, int32_t n, const int32_t* src, const int32_t* to
     }
     last = hop[i];
   }
-  // assign message-window slots; a slot is recycled only after retireHops
+  // assign message-window slots; a slot is recycled only after its topic's retire horizon
   std::vector<int64_t> cnt = g->topicCounter, owner = g->slotOwnerHop;
   std::vector<int32_t> slots(n);
   for (int i = 0; i < n; ++i) {
     const int t = topic[i];
-    const int slot = t * g->St + (int)(cnt[t] % g->St);
+    const int slot = g->lay.slotOf(t, cnt[t]);
     cnt[t]++;
-    if (owner[slot] != INT64_MIN && hop[i] - owner[slot] < g->retireHops) {
-      gs_set_error("message window too small: more than slots_per_topic messages of one topic within " +
-                   std::to_string(g->retireHops) + " hops");
+    if (!gsw::slotFree(owner[slot], hop[i], g->retireOf(t))) {
+      gs_set_error(gsw::guardText(t, g->lay.slots[t], g->retireOf(t), g->windowsSet));
       return GS_ECAPACITY;
     }
     owner[slot] = hop[i];
@@ -1943,6 +1985,40 @@ int gs_publish_ex(gs_engine* g, int32_t n, const int32_t* src, const int32_t* to
     if (ids_out) ids_out[i] = id;
   }
   return g->uploadMessages();
+}
+
+// ---- topic windows (include/gs_window.h)
+int gs_set_topic_windows(gs_engine* g, const int32_t* slots, const int32_t* max_age_hops) {
+  if (g->started || !g->mId.empty()) {
+    gs_set_error("topic windows must be set before the first publish and the first step");
+    return GS_ESTATE;
+  }
+  std::vector<int32_t> s((size_t)g->T, g->cfg.slots_per_topic), a((size_t)g->T, 0);
+  if (slots) s.assign(slots, slots + g->T);
+  if (max_age_hops) a.assign(max_age_hops, max_age_hops + g->T);
+  std::string why = gsw::checkSlots(s.data(), g->T);
+  if (!why.empty()) {
+    gs_set_error(why);
+    return why.find("16384") != std::string::npos ? GS_EUNSUPPORTED : GS_EINVAL;
+  }
+  why = gsw::checkAges(a.data(), g->T);
+  if (!why.empty()) { gs_set_error(why); return GS_EINVAL; }
+  g->setLayout(gsw::makeLayout(s.data(), g->T));
+  g->userAge = a;
+  g->windowsSet = true;
+  g->setWindow();
+  g->slotOwnerHop.assign(g->S, INT64_MIN);
+  g->slotOwnerId.assign(g->S, -1);
+  return GS_OK;
+}
+
+int gs_read_topic_windows(const gs_engine* g, int32_t* slots, int32_t* max_age_hops, int32_t* retire_hops) {
+  for (int t = 0; t < g->T; ++t) {
+    if (slots) slots[t] = g->lay.slots[t];
+    if (max_age_hops) max_age_hops[t] = g->ageOf(t);
+    if (retire_hops) retire_hops[t] = (int32_t)g->retireOf(t);
+  }
+  return GS_OK;
 }
 
 int gs_set_validation(gs_engine* g, const uint8_t* topic_validator, int32_t queue_per_hop) {
@@ -2049,7 +2125,7 @@ int gs_set_topic_score_params(gs_engine* g, int32_t topic, const gs_topic_score_
   if (topic < 0 || topic >= g->T) { gs_set_error("bad topic"); return GS_EINVAL; }
   GS_TRY(gs_validate_topic_score_params(p));
   if (g->started && g->scoring && !g->d.needAge &&
-      p->MeshMessageDeliveriesWindow < g->retireHops * g->cfg.hop_ns) {
+      p->MeshMessageDeliveriesWindow < g->retireOf(topic) * g->cfg.hop_ns) {
     gs_set_error("MeshMessageDeliveriesWindow shorter than the message lifetime can only be set "
                  "before the first step (per-message first-delivery hops are not kept)");
     return GS_EUNSUPPORTED;

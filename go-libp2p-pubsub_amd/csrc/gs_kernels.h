@@ -619,7 +619,7 @@ __global__ void k_pubmask(Dev d, int b, int n, int cur) {
 __device__ __forceinline__ void rs_select(const Dev& d, int u, int64_t base, int deg, int p, uint64_t subp, int slot,
                                           int ff) {
   const int lane = lane_id();
-  const int t = slot / d.St;
+  const int t = slot_topic(d, slot);
   const int origin = d.slotSrc[slot];
   const bool cand = lane < deg && ((subp >> t) & 1) && lane != ff && p != origin;
   const bool fs = cand && d.proto != nullptr && d.proto[base + lane] == GS_PROTO_FLOODSUB;
@@ -649,7 +649,7 @@ __device__ __forceinline__ void rs_select2(const Dev& d, int u, int64_t base, in
   const uint64_t subp = shfl_u64(subpIn, el);
   const int slot = h ? slotB : slotA;
   const int ff = h ? ffB : ffA;
-  const int t = slot / d.St;
+  const int t = slot_topic(d, slot);
   const int origin = d.slotSrc[slot];
   const bool cand = el < deg && ((subp >> t) & 1) && el != ff && p != origin;
   const bool fs = cand && d.proto != nullptr && d.proto[base + el] == GS_PROTO_FLOODSUB;
@@ -790,12 +790,20 @@ constexpr int pa_waves = (!NARROW && !ADV) ? GS_WPE_PA_WIDE : GS_WPE_PA;
 // the senders' frontier bitmaps fb instead of their lists (see "pass 1, dense"
 // below); passes 1b, 2 and 3 are the same code.  amF: the words the node's fb
 // row of this parity may hold bits in (written over in pass 2b).
-template <int WPL, bool NARROW, bool ADV, bool DENSE = false>
+// TAB: topic windows of different sizes (gs_window.h): a slot's topic comes from
+// the word table d.wTopic instead of the multiply.  An instantiation of its
+// own, so that uniform windows run the code they always ran.
+template <int WPL, bool NARROW, bool ADV, bool DENSE = false, bool TAB = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NARROW, ADV>))) void k_phase_a(
     PhaseADev<ADV> dArg, int64_t h, int cur, int head,
                                                 WMask amR, WMask amW, WMask amP, WMask amF, int nR, int nY) {
   static_assert(!(DENSE && ADV), "the dense pass 1 is honest-only");
+  static_assert(!(DENSE && TAB), "the dense pass 1 has one topic");
   const Dev& d = dev_of(dArg);
+  auto topicOf = [&](int slot) -> int {
+    if constexpr (TAB) return (int)d.wTopic[slot >> 6];
+    else return (int)__umulhi((unsigned)slot, d.stMagic);
+  };
   extern __shared__ __attribute__((aligned(16))) uint32_t smem32[];
   const int nCnt = (d.T * d.maxDeg + 7) & ~7;
   const int nCntW = NARROW ? nCnt / 2 : nCnt;             // LDS words of the counter table
@@ -1035,7 +1043,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
       return;
     }
     const int w = slot >> 6;
-    const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+    const int t = topicOf(slot);
     if (trv) trace_emit(d, h, GS_TRACE_COPY, v, d.col[base + i], t, d.slotMid[slot], 2);
     const int kind = kindOf(slot, t);
     if constexpr (ADV) {
@@ -1175,7 +1183,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
             for (int c = 0; c < EPBP; ++c) {
               const uint32_t wd = c < 2 ? q[rr].x : c < 4 ? q[rr].y : c < 6 ? q[rr].z : q[rr].w;
               const int slot = (int)((c & 1) ? (wd >> 16) : (wd & 0xFFFFu));
-              const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+              const int t = topicOf(slot);
               const bool sent = c < n && !(authV && d.slotSrc[slot] == v);  // never to the author
               if (count) {
                 nSent += sent;
@@ -1190,7 +1198,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
             const uint32_t ent = c == 0 ? q[rr].x : (c == 1 ? q[rr].y : (c == 2 ? q[rr].z : q[rr].w));
             const int slot = (int)(ent & 0xFFFF);
             const int tag = (int)(ent >> 16);
-            const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+            const int t = topicOf(slot);
             bool sent = c < n && (tag == 255 ? ((pb >> t) & 1) : ((rl >> t) & 1));
             sent = sent && tag != jri;  // ReceivedFrom exclusion (gossipsub.go:1003)
             if (sent && rsS) sent = (d.sel[(int64_t)uu * d.S + slot] >> jri) & 1;
@@ -1249,7 +1257,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
     const int rk = sRk[slot >> 6];
     if (rk == 0xFFFF || !((sDrop[rk] >> (slot & 63)) & 1)) return;
     if (payloadRpc && gated(i, slot)) return;
-    const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+    const int t = topicOf(slot);
     const int kind = kindOf(slot, t);
     atomicSub(&sPer[i], 1u);
     if (kind == GS_MSG_REJECT) atomicSub(&sInv[i * T + t], 1u);
@@ -1360,7 +1368,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
       for (int k = 0; k < nL; ++k) {
         const uint32_t ent = L[k];
         const int slot = (int)(ent & 0xFFFF), tag = (int)(ent >> 16);
-        const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+        const int t = topicOf(slot);
         bool sent = tag == 255 ? ((pub >> t) & 1) : ((relay >> t) & 1);
         sent = sent && tag != jr;
         if (sent && authV && d.slotSrc[slot] == v) sent = false;
@@ -1379,7 +1387,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
       for (int k = 0; k < Ln; ++k) {
         const uint32_t ent = L[k];
         const int slot = (int)(ent & 0xFFFF), tag = (int)(ent >> 16);
-        const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+        const int t = topicOf(slot);
         bool sent = tag == 255 ? ((pu >> t) & 1) : ((ru >> t) & 1);
         sent = sent && tag != jr;
         if (sent && rs_host(d, u)) sent = (d.sel[(int64_t)u * d.S + slot] >> jr) & 1;
@@ -1422,7 +1430,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
     __syncthreads();  // the queue's LDS again
   };
   eachIr([&](int i, int slot) {
-    if ((sv >> (int)__umulhi((unsigned)slot, d.stMagic)) & 1) deliver(i, slot, false);
+    if ((sv >> topicOf(slot)) & 1) deliver(i, slot, false);
   });
   if constexpr (ADV) {
     if (ctlGated) throttled |= 1ull << lane;
@@ -1503,8 +1511,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
 #pragma unroll
     for (int j = 0; j < WPL; ++j) {
       const int w = lane + 64 * j;
-      const int t = (int)__umulhi((unsigned)(w * 64), d.stMagic);
-      if (!((d.topicVal >> t) & 1)) continue;
+      if (!val_word(d, w)) continue;
       nCand += __popcll(Uw[j] & ~Sw[j]);
     }
     const int candIncl = wave_incl_sum(nCand);
@@ -1518,8 +1525,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
 #pragma unroll
       for (int j = 0; j < WPL; ++j) {
         const int w = lane + 64 * j;
-        const int t = (int)__umulhi((unsigned)(w * 64), d.stMagic);
-        if (!((d.topicVal >> t) & 1)) continue;
+        if (!val_word(d, w)) continue;
         for (uint64_t y = Uw[j] & ~Sw[j]; y; y &= y - 1) sQ[pos++] = (uint32_t)(w * 64 + __ffsll((long long)y) - 1);
       }
       __syncthreads();
@@ -1558,8 +1564,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
 #pragma unroll
         for (int j = 0; j < WPL; ++j) {
           const int w = lane + 64 * j;
-          const int t = (int)__umulhi((unsigned)(w * 64), d.stMagic);
-          if (!((d.topicVal >> t) & 1)) continue;
+          if (!val_word(d, w)) continue;
           uint64_t y = Uw[j] & ~Sw[j];
           while (y) {
             const int b = __ffsll((long long)y) - 1;
@@ -1573,8 +1578,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
 #pragma unroll
       for (int j = 0; j < WPL; ++j) {
         const int w = lane + 64 * j;
-        const int t = (int)__umulhi((unsigned)(w * 64), d.stMagic);
-        if (!((d.topicVal >> t) & 1)) continue;
+        if (!val_word(d, w)) continue;
         uint64_t y = Uw[j] & ~Sw[j];
         while (y) {
           const int b = __ffsll((long long)y) - 1;
@@ -1616,10 +1620,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
     if constexpr (ADV) {
       if (Uw[j]) {
         if (anyDrop) Uw[j] &= ~sDrop[rkw[j]];
-        const int t = (int)__umulhi((unsigned)(w * 64), d.stMagic);
         if (staged) {
-          if ((d.topicVal >> t) & 1) Xw[j] = sD[rkw[j]] & Uw[j];  // the staged verdicts
-        } else if ((d.topicVal >> t) & 1) {
+          if (val_word(d, w)) Xw[j] = sD[rkw[j]] & Uw[j];  // the staged verdicts
+        } else if (val_word(d, w)) {
           // verdicts: REJECT / IGNORE are seen but not delivered
           uint64_t y = Uw[j];
           while (y) {
@@ -1637,7 +1640,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
 #pragma unroll
     for (int j = 0; j < WPL; ++j) {
       uint64_t y = Uw[j] & ~Xw[j];
-      const int t = (int)__umulhi((unsigned)((lane + 64 * j) * 64), d.stMagic);
+      const int t = topicOf(((lane + 64 * j) * 64));
       while (y) {
         const int b = __ffsll((long long)y) - 1;
         y &= y - 1;
@@ -1666,7 +1669,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
         if (x) {
           ++nRejected;
           if (trv)  // validation.go:333 / :351
-            trace_emit(d, h, GS_TRACE_REJECT_MESSAGE, v, d.col[base + ff], (int)__umulhi((unsigned)slot, d.stMagic),
+            trace_emit(d, h, GS_TRACE_REJECT_MESSAGE, v, d.col[base + ff], topicOf(slot),
                        d.slotMid[slot], 2, k == GS_MSG_REJECT ? GS_REJECT_VALIDATION_FAILED : GS_REJECT_VALIDATION_IGNORED);
         }
       }
@@ -1944,7 +1947,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
         for (int k = 0; k < nL; ++k) {
           const uint32_t ent = L[k];
           const int slot = (int)(ent & 0xFFFF), tag = (int)(ent >> 16);
-          const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+          const int t = topicOf(slot);
           bool sent = tag == 255 ? ((pub >> t) & 1) : ((relay >> t) & 1);
           sent = sent && tag != jr;
           if (sent && authV && d.slotSrc[slot] == v) sent = false;
@@ -2021,7 +2024,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pa_waves<NAR
         const int slot = w * 64 + b;
         const int ff = sFirst[fidx(rkw[j], b)];
         if (trv)  // pubsub.go:1057, ReceivedFrom = the first deliverer
-          trace_emit(d, h, GS_TRACE_DELIVER_MESSAGE, v, d.col[base + ff], (int)__umulhi((unsigned)slot, d.stMagic),
+          trace_emit(d, h, GS_TRACE_DELIVER_MESSAGE, v, d.col[base + ff], topicOf(slot),
                      d.slotMid[slot], 2);
         if (pmRow != nullptr)  // DeliverMessage does not add the deliverer to drec.peers
           atomicAnd((unsigned long long*)&pmRow[slot], ~(1ull << ff));
@@ -2147,7 +2150,7 @@ __global__ __launch_bounds__(64) void k_flood_a(Dev d, int64_t h, int cur, WMask
   const int v = d.n0 + blockIdx.x;
   const int lane = lane_id();
   const int prv = cur ^ 1;
-  const int W = d.W, Wt = d.Wt;
+  const int W = d.W;
   const int64_t base = d.rowptr[v];
   const int deg = (int)(d.rowptr[v + 1] - base);
   const uint64_t sv = d.sub[v];
@@ -2187,7 +2190,7 @@ __global__ __launch_bounds__(64) void k_flood_a(Dev d, int64_t h, int cur, WMask
   for (int j = 0; j < WPL; ++j) {
     const int w = lane + 64 * j;
     // v handles the messages of its own topics only (pubsub.go:959)
-    act[j] = w < W && wm_has(amR, w) && ((sv >> (w / Wt)) & 1);
+    act[j] = w < W && wm_has(amR, w) && ((sv >> slot_topic(d, w * 64)) & 1);
     const bool ret = w < W && wm_has(amP, w);
     S[j] = (act[j] || ret) ? d.seen[(int64_t)v * W + w] : 0ull;
     O[j] = act[j] ? d.own[(int64_t)v * W + w] : 0ull;  // v's own messages: nobody sends them back
@@ -2225,7 +2228,7 @@ __global__ __launch_bounds__(64) void k_flood_a(Dev d, int64_t h, int cur, WMask
         acc[j] |= f;
         if (!nb) continue;
         const int w = lane + 64 * j;
-        if ((subI >> (w / Wt)) & 1) {
+        if ((subI >> slot_topic(d, w * 64)) & 1) {
           // v will not send them back to i (ReceivedFrom); those i authored
           // are i's own messages, which i drops itself (O above)
           cnt += __popcll(nb & ~A[q][j]);
@@ -2273,11 +2276,11 @@ __global__ __launch_bounds__(64) void k_flood_a(Dev d, int64_t h, int cur, WMask
   }
 }
 
-// Slots whose message was published more than maxAge hops ago: a first
-// delivery of one of them in hop h is outside the engine's window (E_LATE).
+// Slots whose message was published more than its topic's age limit ago: a
+// first delivery of one of them in hop h is outside the engine's window (E_LATE).
 __global__ void k_oldmask(Dev d, int64_t h) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool old = s < d.S && d.slotSrc[s] >= 0 && d.slotPubHop[s] < h - d.maxAge;
+  const bool old = s < d.S && d.slotSrc[s] >= 0 && d.slotPubHop[s] < h - topic_age(d, slot_topic(d, s < d.S ? s : 0));
   const unsigned long long m = __ballot(old);
   if (s < d.S && (s & 63) == 0) d.oldm[s >> 6] = m;
 }
@@ -2475,7 +2478,7 @@ __global__ __launch_bounds__(64) void k_push(Dev d, int cur) {
   auto dest = [&](uint32_t ent, int& slot) -> uint64_t {
     slot = (int)(ent & 0xFFFF);
     const int tag = (int)(ent >> 16);
-    const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+    const int t = slot_topic(d, slot);
     uint64_t m = tag == 255 ? sMP[t] : (sMR[t] & ~(1ull << (tag & 63)));
     if (rs) m &= d.sel[(int64_t)u * d.S + slot];
     return m;
@@ -2575,7 +2578,7 @@ __global__ __launch_bounds__(64) void k_acct_payload(Dev d, int p) {
     for (int k = 0; k < cnt; ++k) {
       const uint32_t ent = (uint32_t)lane_get((int)mine, k);
       const int slot = (int)(ent & 0xFFFF), tag = (int)(ent >> 16);
-      const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+      const int t = slot_topic(d, slot);
       bool sent = tag == 255 ? ((pu >> t) & 1) : ((ru >> t) & 1);
       sent = sent && tag != lane;  // not back to the deliverer (gossipsub.go:1003)
       if (sent && rsU) sent = (d.sel[(int64_t)u * d.S + slot] >> lane) & 1;
@@ -2612,7 +2615,7 @@ __global__ __launch_bounds__(64) void k_trace_payload(Dev d, int p, int64_t hop)
     for (int k = 0; k < cnt; ++k) {
       const uint32_t ent = (uint32_t)lane_get((int)mine, k);
       const int slot = (int)(ent & 0xFFFF), tag = (int)(ent >> 16);
-      const int t = (int)__umulhi((unsigned)slot, d.stMagic);
+      const int t = slot_topic(d, slot);
       bool sent = tr && (tag == 255 ? ((pu >> t) & 1) : ((ru >> t) & 1));
       sent = sent && tag != lane;  // not back to the deliverer (gossipsub.go:1003)
       if (sent && rs_host(d, u)) sent = (d.sel[(int64_t)u * d.S + slot] >> lane) & 1;

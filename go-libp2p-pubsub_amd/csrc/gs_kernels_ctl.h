@@ -303,7 +303,7 @@ __device__ __forceinline__ void put_served(const Dev& d, const int32_t* pool, co
   for (int q = 0; q < n; ++q)
     if (flags == nullptr || flags[off + q]) {
       const int slot = pool[off + q];
-      put(GS_RPC_ITEM_MSG, (int)__umulhi((unsigned)slot, d.stMagic), d.slotMid[slot]);
+      put(GS_RPC_ITEM_MSG, slot_topic(d, slot), d.slotMid[slot]);
     }
 }
 
@@ -355,6 +355,10 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
   const int prv = cur ^ 1;
   const int W = d.W;
   const int Wt = d.Wt;
+  // a topic's first word (t = T: the end of the last): the prefix table when the
+  // topic windows differ in size (gs_window.h), else the multiply
+  const bool tabW = d.stMagic == 0u;
+  auto tw0 = [&](int t) -> int { return tabW ? (int)d.tW0[t] : t * Wt; };
   const int64_t base = d.rowptr[v];
   const int deg = (int)(d.rowptr[v + 1] - base);
   const uint64_t sv = d.sub[v];
@@ -762,7 +766,7 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
             if (srv) {
               d.pool[cur][sOut[i] + atomicAdd(&sCur[i], 1)] = slot;
               if (d.rpcB != nullptr)
-                atomicAdd(sp ? &sSrvBS[i] : &sSrvB[i], (uint32_t)d.acc[(int)__umulhi((unsigned)slot, d.stMagic)].msgF);
+                atomicAdd(sp ? &sSrvBS[i] : &sSrvB[i], (uint32_t)d.acc[slot_topic(d, slot)].msgF);
             }
           });
         }
@@ -791,7 +795,11 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
     // config3's 157) (sender, topic, 16-word chunk), so the lanes share the
     // words of one topic; a cut is decided per (sender, topic) item tb = b / nCh
     // and applied to each of its chunks.  At most 64 items per sender.
-    const int nCh = Wt <= 16 ? 1 : (Wt + 15) >> 4;
+    int chW = 16, nCh = Wt <= 16 ? 1 : (Wt + 15) >> 4;  // (Wt: the largest topic's words)
+    while (d.T * nCh > 64) {  // uneven topic windows only: wider chunks keep a sender's items within 64
+      chW *= 2;
+      nCh = (Wt + chW - 1) / chW;
+    }
     sIt[lane] = lane_prefix(__popcll(tm) * nCh, &totalItems);
     sTm[lane] = tm;
     sNode[lane] = u;
@@ -841,12 +849,13 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
         const int i = item_sender(sIt, tb * nCh, k);
         const int t = kth_bit(sTm[i], k / nCh);
         const int uu = sNode[i];
+        const int wA = tw0(t), wZ = tw0(t + 1);
         int nm = 0;
         if (waveSum) {
-          for (int w = t * Wt + lane; w < (t + 1) * Wt; w += 64) nm += __popcll(d.gw[(int64_t)uu * W + w]);
+          for (int w = wA + lane; w < wZ; w += 64) nm += __popcll(d.gw[(int64_t)uu * W + w]);
           nm = wave_last(wave_incl_sum(nm));
         } else {
-          for (int w = t * Wt; w < (t + 1) * Wt; ++w) nm += __popcll(d.gw[(int64_t)uu * W + w]);
+          for (int w = wA; w < wZ; ++w) nm += __popcll(d.gw[(int64_t)uu * W + w]);
         }
         if (nm > d.MaxIHaveLength && (!waveSum || lane == 0)) {
           atomicAdd(cN, 1);
@@ -881,7 +890,9 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
         const int i = item_sender(sIt, tb * nCh, k);
         const int t = kth_bit(sTm[i], k / nCh);
         const int uu = sNode[i];
-        const uint64_t* const g = d.gw + (int64_t)uu * W + t * Wt;  // the sender's words of topic t
+        const int wT = tw0(t);
+        const uint64_t* const g = d.gw + (int64_t)uu * W + wT;  // the sender's words of topic t
+        const int Wt = tw0(t + 1) - wT;  // (its own count: shadows the largest)
         int nm = 0;  // its ids
         for (int w = lane; w < Wt; w += 64) nm += __popcll(g[w]);
         nm = wave_last(wave_incl_sum(nm));
@@ -962,7 +973,7 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
             for (int q = 0; q < GS_CUTQ; ++q) {
               m0[q] = m1[q] = 0;
               if (bs[q] >= 0) {  // both ids of the pair (bs even: a 16-byte aligned load)
-                const int4 p = *reinterpret_cast<const int4*>(d.slotMid + (int64_t)(t * Wt + ws[q]) * 64 + bs[q]);
+                const int4 p = *reinterpret_cast<const int4*>(d.slotMid + (int64_t)(wT + ws[q]) * 64 + bs[q]);
                 m0[q] = (int64_t)(((uint64_t)(uint32_t)p.y << 32) | (uint32_t)p.x);
                 m1[q] = (int64_t)(((uint64_t)(uint32_t)p.w << 32) | (uint32_t)p.z);
               }
@@ -1025,8 +1036,9 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
       unsigned long long K = 0;
       long long M = 0;
       const bool cut = cutOf(b / nCh, K, M);  // the (sender, topic) item's cut
-      const int wBeg = nCh > 1 ? t * Wt + 16 * ch : t * Wt;
-      const int wEnd = nCh > 1 ? min(wBeg + 16, (t + 1) * Wt) : (t + 1) * Wt;
+      const int wZ = tw0(t + 1);
+      const int wBeg = tw0(t) + (nCh > 1 ? chW * ch : 0);
+      const int wEnd = nCh > 1 ? min(wBeg + chW, wZ) : wZ;  // (a shorter topic's trailing chunks: empty)
       for (int w0 = wBeg; w0 < wEnd; w0 += 4) {
         uint64_t g[4];
 #pragma unroll
@@ -1127,7 +1139,7 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
             unsigned long long cK0 = 0;
             long long cM0 = 0;
             const bool cut = cutOf(b, cK0, cM0);
-            for (int w = t * Wt + lane; w < (t + 1) * Wt; w += 64) {
+            for (int w = tw0(t) + lane, wZ = tw0(t + 1); w < wZ; w += 64) {
               uint64_t y = d.gw[(int64_t)uu * W + w] & ~sseen[w];
               while (y) {
                 const int bb = __ffsll((long long)y) - 1;
@@ -1891,7 +1903,7 @@ __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, 
   // lane t: message ids of topic t in the gossip windows (emitGossip's mids)
   int nmT = 0;
   if (lane < d.T)
-    for (int w = lane * d.Wt; w < (lane + 1) * d.Wt; ++w) nmT += __popcll(sgw[w]);
+    for (int w = topic_w0(d, lane), wZ = topic_w0(d, lane + 1); w < wZ; ++w) nmT += __popcll(sgw[w]);
   const uint64_t subv = vm && edge_up(d, e) ? d.subA[vcol] : 0;  // topic peers: connected, announced
   // the candidates of getPeers and emitGossip: mesh-capable topic peers
   // (GossipSubFeatureMesh, gossipsub.go:1681, 1849)
@@ -2022,7 +2034,7 @@ __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, 
         int nIh = 0;
         for (uint64_t m = ihave; m; m &= m - 1) {
           const int t = __ffsll((long long)m) - 1;
-          for (int w = t * d.Wt; w < (t + 1) * d.Wt; ++w) nIh += __popcll(gwWord(w));
+          for (int w = topic_w0(d, t), wZ = topic_w0(d, t + 1); w < wZ; ++w) nIh += __popcll(gwWord(w));
         }
         const int64_t pxr = d.doPX ? d.cPx[cur][re] : -1;
         rpc_trace(d, hop, v, vcol, 4, 3, GS_RPC_ORD(4, 0),
@@ -2034,7 +2046,7 @@ __global__ __launch_bounds__(64) GS_OCC_HB void k_heartbeat(Dev d, int64_t hop, 
                     px_each(d, cur, pxr, toprune, [&](int tt, int q) { put(GS_RPC_ITEM_PX, tt, q); });
                     for (uint64_t m = ihave; m; m &= m - 1) {
                       const int t = __ffsll((long long)m) - 1;
-                      for (int w = t * d.Wt; w < (t + 1) * d.Wt; ++w)
+                      for (int w = topic_w0(d, t), wZ = topic_w0(d, t + 1); w < wZ; ++w)
                         for (uint64_t y = gwWord(w); y; y &= y - 1)
                           put(GS_RPC_ITEM_IHAVE, t, d.slotMid[(int64_t)w * 64 + __ffsll((long long)y) - 1]);
                     }
@@ -2155,7 +2167,7 @@ __global__ void k_read_deliv(Dev d, int slot, int64_t pubhop, int32_t* hop, int3
   // a rejected / ignored message is seen but never delivered (the author's own
   // publish is), a phantom id is never delivered at all
   const int kind = d.slotKind[slot];
-  const int t = slot / d.St;
+  const int t = slot_topic(d, slot);
   if (kind == GS_MSG_PHANTOM) s = false;
   if ((kind == GS_MSG_REJECT || kind == GS_MSG_IGNORE) && ((d.topicVal >> t) & 1) && d.slotSrc[slot] != v) s = false;
   if (!s) { hop[v] = -1; from[v] = -1; return; }

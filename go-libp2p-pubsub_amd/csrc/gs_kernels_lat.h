@@ -83,7 +83,7 @@ __global__ __launch_bounds__(GS_LAT_BLOCK) void k_lat_count(Dev d, int cur, WMas
 // per-message table and is added to entry (topic, a) of the per-topic one, a =
 // h - slotPubHop[s]; latCnt is left zero for the next hop.  A (slot, age) pair
 // is touched in one hop only, so the per-message store needs no atomic.  An
-// age outside [0, maxAge] is dropped: that hop fails with E_LATE.
+// age outside [0, the topic's own limit] is dropped: that hop fails with E_LATE.
 __global__ void k_lat_fold(Dev d, int64_t h, int bins, uint32_t* __restrict__ mhist,
                            unsigned long long* __restrict__ hist) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,9 +92,10 @@ __global__ void k_lat_fold(Dev d, int64_t h, int bins, uint32_t* __restrict__ mh
   if (c == 0) return;
   d.latCnt[s] = 0u;
   const int64_t a = h - d.slotPubHop[s];
-  if (a < 0 || a >= bins) return;
+  const int t = slot_topic(d, s);
+  if (a < 0 || a >= bins || a > topic_age(d, t)) return;
   mhist[(int64_t)s * bins + a] = c;
-  atomicAdd(&hist[(int64_t)__umulhi((unsigned)s, d.stMagic) * bins + a], (unsigned long long)c);
+  atomicAdd(&hist[(int64_t)t * bins + a], (unsigned long long)c);
 }
 
 // The per-message rows of the slots this hop's publishes take over start from

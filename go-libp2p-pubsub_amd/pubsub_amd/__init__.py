@@ -17,6 +17,6 @@ from .engine import (PRODUCT_LIB, Engine, GossipEngineError, NewFloodSub, NewGos
                      NewRandomSub, PROTOCOLS, WithDevice, WithEventTracer, encode_trace, WithDirectPeers, WithFloodPublish, WithGossipSubParams,
                      WithHop, WithMessageWindow, WithPartition, WithPeerScore, WithPeertxCapacity, WithFrontierLists, WithFrontierBitmaps, WithRecordDeliveries, WithSeed,
                      WithBehaviour, WithPeerGater, WithRPCAccounting, WithValidation, WithPeerExchange, WithDormant,
-                     WithRouters, WithProtocols, WithIPWhitelist, WithLatencyStats, latency_quantiles,
+                     WithRouters, WithProtocols, WithIPWhitelist, WithLatencyStats, WithTopicWindows, latency_quantiles,
                      WithPeerScoreInspect, PeerScoreSnapshot, TopicScoreSnapshot, default_inspect_bounds,
                      load)

@@ -226,6 +226,12 @@ LATENCY_FUNCTIONS = [
     ("gs_read_latency_kernel_stats", C.c_int, [P, C.POINTER(f64), C.POINTER(i64)]),
 ]
 
+# include/gs_window.h (product library only; bound by Engine when present)
+WINDOW_FUNCTIONS = [
+    ("gs_set_topic_windows", C.c_int, [P, C.POINTER(i32), C.POINTER(i32)]),
+    ("gs_read_topic_windows", C.c_int, [P, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+]
+
 # include/gs_inspect.h (product library only; bound by Engine with WithPeerScoreInspect)
 GS_INSPECT_MAX_BOUNDS = 63
 GS_INSPECT_DEG_BINS = 65  # mesh degree 0..64

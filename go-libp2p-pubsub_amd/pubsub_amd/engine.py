@@ -94,6 +94,19 @@ def WithMessageWindow(slots_per_topic):
     return ("slots_per_topic", int(slots_per_topic))
 
 
+def WithTopicWindows(slots=None, max_age_hops=None):
+    """The message window per topic (include/gs_window.h): slots[t] is topic t's
+    ring (a positive multiple of 64, default WithMessageWindow's value for every
+    topic; at most 16384 in total) and max_age_hops[t] > 0 the age in hops up to
+    which a first delivery of a message of topic t is accepted (0 or None: the
+    engine's policy, 3 heartbeats for honest runs).  A hot topic among many
+    takes a large ring and the others small ones; a sparsely subscribed topic
+    takes a long age.  The CPU oracle has no window: there the option is
+    accepted and does nothing.  Read with Engine.topic_windows()."""
+    conv = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    return ("topic_windows", (conv(slots), conv(max_age_hops)))
+
+
 def WithRecordDeliveries(on=True):
     return ("record", bool(on))
 
@@ -335,6 +348,19 @@ class Engine:
             C.byref(thr_c) if thr_c is not None else None,
             C.byref(opts["gater"].to_c()) if opts.get("gater") is not None else None, C.byref(h)))
         self.h = h
+        # include/gs_window.h: exported by the product library only
+        self._has_windows = all(hasattr(self.lib, name) for name, _, _ in _abi.WINDOW_FUNCTIONS)
+        if self._has_windows:
+            for name, res, args in _abi.WINDOW_FUNCTIONS:
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = res, args
+        tw = opts.get("topic_windows")
+        if tw is not None and self._has_windows:  # (the oracle has no window)
+            for a, what in zip(tw, ("slots", "max_age_hops")):
+                if a is not None and len(a) != num_topics:
+                    self.close()
+                    raise ValueError(f"WithTopicWindows: {what} needs one entry per topic ({num_topics}), got {len(a)}")
+            _check(self.lib, self.lib.gs_set_topic_windows(h, _ptr(tw[0], C.c_int32), _ptr(tw[1], C.c_int32)))
         rowptr, col, outbound = graph
         self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
         self.col = np.ascontiguousarray(col, dtype=np.int32)
@@ -629,6 +655,17 @@ class Engine:
                 return np.concatenate(parts)
 
     # ---------------------------------------------------------------- latency statistics
+    def topic_windows(self):
+        """(slots, max_age_hops, retire_hops), int32 [T] each: the message window
+        in force per topic (gs_read_topic_windows): its ring, the age up to which
+        a first delivery is accepted, and the hops after which its slots are
+        taken again.  Product library only."""
+        if not self._has_windows:
+            raise ValueError("topic windows (WithTopicWindows): product library only")
+        out = [np.zeros(self.T, dtype=np.int32) for _ in range(3)]
+        _check(self.lib, self.lib.gs_read_topic_windows(self.h, *[_ptr(a, C.c_int32) for a in out]))
+        return tuple(out)
+
     def _latency_lib(self):
         if not self._has_latency:
             raise ValueError("latency statistics (WithLatencyStats): product library only")

@@ -8,7 +8,8 @@
  *     a = delivery hop - publish hop,  1 <= a <= maxAge,
  * into two tables of bins = maxAge + 1 entries per row (index = age, bin 0
  * stays 0; a first delivery later than maxAge fails the step, so there is no
- * overflow bin):
+ * overflow bin; with per-topic age limits, gs_window.h, maxAge is the largest
+ * topic's and a topic's bins past its own limit stay 0):
  *   per topic    hist[t][a], int64, since the start or the last reset;
  *   per message  mhist[a], uint32, of the message that owns its slot; readable
  *                while the slot is not recycled (the rule of
