@@ -26,6 +26,7 @@
 #include "../../include/gs_trace.h"
 #include "../../include/gs_latency.h"
 #include "../../include/gs_inspect.h"
+#include "../../include/gs_mesh_health.h"
 #include "../../include/gs_window.h"
 #include "gs_window_layout.h"
 #include "gs_host.h"
@@ -33,6 +34,7 @@
 #include "gs_kernels_ctl.h"
 #include "gs_kernels_lat.h"
 #include "gs_kernels_insp.h"
+#include "gs_kernels_mesh.h"
 #include "gs_exchange.h"
 
 #define HIPCHECK(expr)                                                        \
@@ -424,16 +426,29 @@ struct gs_engine {
   unsigned inspGrid = 0;
   int inspRowLen() const { return insp_row_len((int)inspBounds.size(), T); }
   size_t inspExtLen() const { return inspEdges.size() * (3 + 4 * (size_t)T); }  // 8-byte words per tick
+  // mesh health (gs_mesh_health.h): the label and size tables (uint32 [N][T]),
+  // a ring of meshCap rows (mesh_row_len), the batch's flags and the word count
+  bool meshOn = false, meshLabels = false;
+  int64_t meshPeriod = 0, meshTaken = 0;
+  int meshCap = 0;
+  std::vector<uint8_t> meshMask;     // [N] the hosts counted, or empty for all
+  uint8_t* dMeshMask = nullptr;
+  uint32_t *dMeshL = nullptr, *dMeshZ = nullptr, *dMeshFlag = nullptr;  // flags: [GS_MESH_BATCH + 1]
+  unsigned long long *dMeshRows = nullptr, *dMeshWords = nullptr;
+  unsigned meshGrid = 0;
+  int64_t meshIters = 0, meshBytes = 0;  // since the start or the last gs_set_profiling
   // kernel timing: (kernel id, start event, end event) pending until a sync
   bool profiling = false;
   std::vector<hipEvent_t> evPool;
   size_t evUsed = 0;
   std::vector<int> pendKid;
   // (past the public kernel ids: the latency kernels, gs_read_latency_kernel_stats, and the
-  // inspection's three passes, gs_read_inspect_kernel_stats)
+  // inspection's three passes, gs_read_inspect_kernel_stats; mesh health's four,
+  // gs_read_mesh_health_kernel_stats)
   static constexpr int kLatCount = GS_NUM_KERNELS, kLatFold = GS_NUM_KERNELS + 1;
   static constexpr int kInspScore = GS_NUM_KERNELS + 2, kInspReduce = GS_NUM_KERNELS + 3;
-  static constexpr int kInspGather = GS_NUM_KERNELS + 4, kTimed = GS_NUM_KERNELS + 5;
+  static constexpr int kInspGather = GS_NUM_KERNELS + 4, kMeshInit = GS_NUM_KERNELS + 5;
+  static constexpr int kTimed = kMeshInit + 4;  // (kMeshInit + GS_MESH_K_*)
   double kMs[kTimed] = {0};
   int64_t kLaunches[kTimed] = {0};
   hipEvent_t nextEvent() {
@@ -526,6 +541,10 @@ struct gs_engine {
     dInspEdges = nullptr;
     inspEdges.clear();
     inspTaken = 0;
+    dMeshMask = nullptr;
+    dMeshL = dMeshZ = dMeshFlag = nullptr;
+    dMeshRows = dMeshWords = nullptr;
+    meshTaken = 0;
     started = churnOn = allocFailed = false;
     uploaded = 0;
     aliveH.clear();
@@ -597,6 +616,7 @@ struct gs_engine {
   int retireAndPublish(const Hop& hp), phaseB(const Hop& hp);
   int allocLatency(), latencyStats(const Hop& hp);
   int allocInspect(), inspectTick();
+  int allocMeshHealth(), meshTick();
   void refreshOrFold(const Hop& hp), heartbeat(const Hop& hp);
   template <bool ADV>
   PhaseADev<ADV> phaseADev() const {

@@ -177,6 +177,7 @@ int gs_engine::buildDevice(const Plan& pl) {
   GS_TRY(allocPartition());
   GS_TRY(allocLatency());
   GS_TRY(allocInspect());
+  GS_TRY(allocMeshHealth());
   GS_TRY(allocFail("state", "; reduce num_nodes or slots_per_topic"));
   GS_TRY(initConnections(pl));
   GS_TRY(allocAcct(pl));
@@ -740,6 +741,88 @@ int gs_engine::inspectTick() {
   return GS_OK;
 }
 
+// Mesh health (gs_mesh_health.h) at its exact sizes: the two [N][T] tables, the
+// ring of rows, the include mask, a batch's flags and the word counter; the
+// grid of the three node passes.
+int gs_engine::allocMeshHealth() {
+  if (!meshOn) return GS_OK;
+  const size_t nt = (size_t)N * (size_t)T;
+  const bool before = allocFailed;
+  allocFailed = false;
+  dMeshL = dalloc<uint32_t>(nt);
+  dMeshZ = dalloc<uint32_t>(nt);
+  dMeshRows = dalloc<unsigned long long>((size_t)meshCap * (size_t)mesh_row_len(T));
+  dMeshFlag = dalloc<uint32_t>(GS_MESH_BATCH + 1);
+  dMeshWords = dalloc<unsigned long long>(1);
+  if (!meshMask.empty()) dMeshMask = dalloc<uint8_t>((size_t)N);
+  if (allocFailed) return allocFail("mesh health tables", "; reduce ticks or num_nodes");
+  allocFailed = before;
+  GS_TRY(putNow(dMeshMask, meshMask.data(), meshMask.size()));
+  int cus = 0;
+  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
+  meshGrid = std::min<unsigned>(GS_MESH_WGS_PER_CU * (unsigned)std::max(cus, 1),
+                                std::max(nblk(mesh_groups(N, T), GS_MESH_BLOCK / 64), 1u));
+  return GS_OK;
+}
+
+// A tick at the end of a hop (`hop` already counts it): labels to their fixed
+// point in batches of GS_MESH_BATCH iterations, the host reading the batch's
+// flags in between (flag[i] != 0: iteration i of the batch had work and ran;
+// the last flag 0: the labels have settled), at most N iterations in all; then
+// the sizes and the row.  The byte count: what every pass streams, from the
+// shapes, plus the label words the kernels counted.
+int gs_engine::meshTick() {
+  unsigned long long* row = dMeshRows + (size_t)(meshTaken % meshCap) * (size_t)mesh_row_len(T);
+  const int64_t nt = (int64_t)N * T;
+  const bool wide = mesh_tp(T) == 64;
+  HIPCHECK(hipMemsetAsync(row, 0, (size_t)mesh_row_len(T) * 8, stream));
+  HIPCHECK(hipMemsetAsync(dMeshWords, 0, 8, stream));
+  TIMED(this, kMeshInit + GS_MESH_K_INIT,
+        (k_mesh_init<<<nblk(nt, 256), 256, 0, stream>>>(d, dMeshMask, dMeshL, dMeshZ)));
+  int64_t iters = 0;
+  for (bool settled = false; !settled;) {
+    const int n = (int)std::min<int64_t>(GS_MESH_BATCH, (int64_t)N - iters);
+    if (n <= 0) {
+      gs_set_error("mesh health: labels did not converge after " + std::to_string(iters) + " iterations (hop " +
+                   std::to_string(hop) + ")");
+      return GS_EDEVICE;
+    }
+    HIPCHECK(hipMemsetAsync(dMeshFlag, 0, (size_t)(GS_MESH_BATCH + 1) * 4, stream));
+    HIPCHECK(hipMemsetAsync(dMeshFlag, 1, 4, stream));  // non-zero: the batch's first iteration runs
+    for (int i = 0; i < n; ++i)
+      with_consts([&](auto w) {
+        TIMED(this, kMeshInit + GS_MESH_K_LABEL,
+              (k_mesh_label<CV(w)><<<meshGrid, GS_MESH_BLOCK, 0, stream>>>(d, dMeshL, dMeshFlag + i, dMeshWords)));
+      }, Flag{wide});
+    uint32_t flag[GS_MESH_BATCH + 1];
+    HIPCHECK(hipMemcpyAsync(flag, dMeshFlag, sizeof flag, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    for (int i = 0; i < n; ++i) iters += flag[i] != 0u;
+    settled = flag[n] == 0u;
+  }
+  TIMED(this, kMeshInit + GS_MESH_K_SIZES,
+        (k_mesh_sizes<<<meshGrid, GS_MESH_BLOCK, 0, stream>>>(d, dMeshL, dMeshZ, dMeshWords)));
+  with_consts([&](auto w) {
+    TIMED(this, kMeshInit + GS_MESH_K_ROW,
+          (k_mesh_row<CV(w)><<<meshGrid, GS_MESH_BLOCK, 0, stream>>>(d, dMeshMask, dMeshL, dMeshZ, row)));
+  }, Flag{wide});
+  HIPCHECK(hipGetLastError());
+  unsigned long long words = 0;
+  HIPCHECK(hipMemcpyAsync(&words, dMeshWords, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHECK(hipStreamSynchronize(stream));
+  // per edge: mesh word, reverse edge, peer, the reverse edge's mesh word (the
+  // row pass: the peer's include byte too); per node: its CSR row bounds
+  const int64_t edgeWalk = E * (8 + 4 + 4 + 8) + (int64_t)N * 8;
+  meshIters += iters;
+  meshBytes += nt * 8 + (int64_t)N * 10          // init: two stores; the subscription word, router and include bytes
+               + iters * (edgeWalk + nt * 4)     // an iteration: the edges and the nodes' own labels
+               + nt * 4                          // sizes: every label
+               + nt * 4 + edgeWalk + E           // row: every label, the edges
+               + (int64_t)words * 4;             // what the label and size passes counted besides
+  meshTaken++;
+  return GS_OK;
+}
+
 int gs_engine::allocTrace() {
   Dev& x = d;
   if (traceMask.empty()) return GS_OK;
@@ -1103,6 +1186,7 @@ int gs_engine::stepOne() {
   if (world > 1) GS_TRY(exchange(hp.cur, heartbeatDue(hp.now)));
   hop++;
   if (inspOn && hop % inspPeriod == 0) GS_TRY(inspectTick());
+  if (meshOn && hop % meshPeriod == 0) GS_TRY(meshTick());
   return GS_OK;
 }
 
@@ -2151,6 +2235,7 @@ int gs_set_topic_score_params(gs_engine* g, int32_t topic, const gs_topic_score_
 int gs_set_partition(gs_engine* g, int32_t rank, int32_t world, const gs_transport* tr) {
   if (g->started) { gs_set_error("the partition must be set before the first step"); return GS_ESTATE; }
   if (world < 1 || world > 255 || rank < 0 || rank >= world) { gs_set_error("bad rank / world"); return GS_EINVAL; }
+  if (world > 1 && g->meshOn) { gs_set_error("mesh health: not on a partitioned engine"); return GS_EUNSUPPORTED; }
   if (world > 1 && (!tr || !tr->allgather_i64 || !tr->allgather || !tr->alltoallv)) {
     gs_set_error("a partitioned engine needs a transport with allgather_i64, allgather and alltoallv");
     return GS_EINVAL;
@@ -2693,6 +2778,85 @@ int gs_read_inspect_kernel_stats(gs_engine* g, double* total_ms, int64_t* launch
   return GS_OK;
 }
 
+// ---- mesh health (include/gs_mesh_health.h)
+int gs_set_mesh_health(gs_engine* g, const gs_mesh_health_config* c) {
+  if (g->started) { gs_set_error("the mesh health inspector must be set before the first step"); return GS_ESTATE; }
+  if (g->meshOn) { gs_set_error("duplicate mesh health inspector"); return GS_ESTATE; }
+  if (g->cfg.router != GS_ROUTER_GOSSIPSUB) { gs_set_error("pubsub router is not gossipsub"); return GS_EUNSUPPORTED; }
+  if (g->world > 1) { gs_set_error("mesh health: not on a partitioned engine"); return GS_EUNSUPPORTED; }
+  if (!c || c->period_hops <= 0) { gs_set_error("mesh health: period_hops must be positive"); return GS_EINVAL; }
+  if (c->ticks < 1) { gs_set_error("mesh health: ticks must be at least 1"); return GS_EINVAL; }
+  g->meshPeriod = c->period_hops;
+  g->meshCap = c->ticks;
+  g->meshMask.clear();
+  if (c->include) g->meshMask.assign(c->include, c->include + g->N);
+  g->meshLabels = c->labels != 0;
+  g->meshOn = true;
+  return GS_OK;
+}
+
+static int mesh_on(const gs_engine* g) {
+  if (!g->meshOn) { gs_set_error("mesh health is off (gs_set_mesh_health)"); return GS_ESTATE; }
+  return GS_OK;
+}
+
+int64_t gs_mesh_health_ticks(const gs_engine* g) {
+  GS_TRY(mesh_on(g));
+  return g->meshTaken;
+}
+
+// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
+int gs_read_mesh_health_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* row, int64_t* comp_hist) {
+  GS_TRY(mesh_on(g));
+  if (tick < 0 || tick >= g->meshTaken) {
+    gs_set_error("mesh health: tick " + std::to_string(tick) + " not taken yet (" + std::to_string(g->meshTaken) +
+                 " so far)");
+    return GS_EINVAL;
+  }
+  if (tick < g->meshTaken - g->meshCap) {
+    gs_set_error("mesh health: tick " + std::to_string(tick) + " already overwritten (ring of " +
+                 std::to_string(g->meshCap) + ")");
+    return GS_ESTATE;
+  }
+  if (hop) *hop = (tick + 1) * g->meshPeriod;
+  const size_t nf = (size_t)g->T * GS_MESH_ROW_FIELDS;
+  const unsigned long long* src = g->dMeshRows + (size_t)(tick % g->meshCap) * (size_t)mesh_row_len(g->T);
+  if (row) HIPCHECK(hipMemcpyAsync(row, src, nf * 8, hipMemcpyDeviceToHost, g->stream));
+  if (comp_hist)
+    HIPCHECK(hipMemcpyAsync(comp_hist, src + nf, (size_t)g->T * GS_MESH_SIZE_BINS * 8, hipMemcpyDeviceToHost,
+                            g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+// The label table is the newest tick's until the next tick starts over.
+int gs_read_mesh_labels(gs_engine* g, int64_t* tick, int32_t* labels) {
+  GS_TRY(mesh_on(g));
+  if (!g->meshLabels) { gs_set_error("mesh health: the label table is not kept (labels = 0)"); return GS_ESTATE; }
+  if (g->meshTaken == 0) { gs_set_error("mesh health: no tick taken yet"); return GS_EINVAL; }
+  if (tick) *tick = g->meshTaken - 1;
+  if (labels)  // GS_MESH_NONE reads -1
+    HIPCHECK(hipMemcpyAsync(labels, g->dMeshL, (size_t)g->N * (size_t)g->T * 4, hipMemcpyDeviceToHost, g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_mesh_health_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
+  GS_TRY(mesh_on(g));
+  if (g->started) {
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    g->resolveTimings();
+  }
+  for (int i = 0; i < GS_MESH_ST_ITERS; ++i) {
+    total_ms[i] = g->kMs[gs_engine::kMeshInit + i];
+    launches[i] = g->kLaunches[gs_engine::kMeshInit + i];
+  }
+  total_ms[GS_MESH_ST_ITERS] = total_ms[GS_MESH_ST_BYTES] = 0.0;
+  launches[GS_MESH_ST_ITERS] = g->meshIters;
+  launches[GS_MESH_ST_BYTES] = g->meshBytes;
+  return GS_OK;
+}
+
 #ifdef GS_STAMPS
 // Debug build: phase-A cycle stamps of the sampled nodes of the last hop.
 int gs_debug_stamps(gs_engine* g, unsigned long long* out, int n) {
@@ -2715,6 +2879,7 @@ int gs_set_profiling(gs_engine* g, int on) {
   }
   g->profiling = on != 0;
   for (int i = 0; i < gs_engine::kTimed; ++i) { g->kMs[i] = 0; g->kLaunches[i] = 0; }
+  g->meshIters = g->meshBytes = 0;
   return GS_OK;
 }
 

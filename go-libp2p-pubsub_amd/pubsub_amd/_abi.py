@@ -258,6 +258,26 @@ INSPECT_FUNCTIONS = [
 ]
 INSPECT_KERNEL_NAMES = ["insp_score", "insp_reduce", "insp_gather"]
 
+# include/gs_mesh_health.h (product library only; bound by Engine with WithMeshHealth)
+GS_MESH_SIZE_BINS = 32
+MESH_ROW_FIELDS = ["members", "components", "largest", "isolated", "one_sided", "outside", "eclipsed"]
+
+
+class MeshHealthConfigC(C.Structure):
+    _fields_ = [("period_hops", i64), ("ticks", i32), ("include", C.POINTER(u8)), ("labels", i32)]
+
+
+MESH_HEALTH_FUNCTIONS = [
+    ("gs_set_mesh_health", C.c_int, [P, C.POINTER(MeshHealthConfigC)]),
+    ("gs_mesh_health_ticks", i64, [P]),
+    ("gs_read_mesh_health_row", C.c_int, [P, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    ("gs_read_mesh_labels", C.c_int, [P, C.POINTER(i64), C.POINTER(i32)]),
+    ("gs_read_mesh_health_kernel_stats", C.c_int, [P, C.POINTER(f64), C.POINTER(i64)]),
+]
+# the four passes (total_ms, launches), then two counts
+MESH_KERNEL_NAMES = ["mesh_init", "mesh_label", "mesh_sizes", "mesh_row"]
+MESH_STAT_NAMES = MESH_KERNEL_NAMES + ["iterations", "bytes"]
+
 KERNEL_NAMES = ["score", "refresh", "join", "fanout", "fwd", "phase_a", "publish", "phase_b",
                 "hb_pre", "heartbeat", "push"]
 

@@ -286,11 +286,23 @@ def WithPeerScoreInspect(inspect, period, *, bounds=None, nodes=None, ticks=64, 
                                   extended=bool(extended)))
 
 
-def _inspect_period_hops(period, hop_ns):
+def _inspect_period_hops(period, hop_ns, what="WithPeerScoreInspect"):
     if period <= 0 or period % hop_ns:
-        raise ValueError(f"WithPeerScoreInspect: period {period} ns must be a positive multiple of the hop "
-                         f"({hop_ns} ns)")
+        raise ValueError(f"{what}: period {period} ns must be a positive multiple of the hop ({hop_ns} ns)")
     return period // hop_ns
+
+
+def WithMeshHealth(period, *, nodes=None, ticks=64, labels=False):
+    """Mesh health (include/gs_mesh_health.h, product library only): every
+    `period` (ns, a positive multiple of the hop) the engine counts, inside
+    step(), each topic's mesh components over the mutual mesh edges of the
+    hosts in `nodes` (a bool or byte mask over the hosts; None: all), and the
+    one-sided, outside and eclipsed mesh entries, into a ring of `ticks` ticks;
+    labels=True keeps the newest tick's component labels readable.  Read with
+    Engine.mesh_health_row(), mesh_labels().  Not on a partitioned engine."""
+    if int(ticks) < 1:
+        raise ValueError("WithMeshHealth: ticks must be at least 1")
+    return ("mesh_health", dict(period=int(period), nodes=nodes, ticks=int(ticks), labels=bool(labels)))
 
 
 def WithPartition(rank, world, transport):
@@ -320,6 +332,11 @@ class Engine:
         insp = opts.get("score_inspect")
         if insp is not None:  # refused before anything is created
             insp = dict(insp, period_hops=_inspect_period_hops(insp["period"], cfg.hop_ns))
+        mh = opts.get("mesh_health")
+        if mh is not None:
+            mh = dict(mh, period_hops=_inspect_period_hops(mh["period"], cfg.hop_ns, "WithMeshHealth"))
+            if mh["nodes"] is not None and len(mh["nodes"]) != num_nodes:
+                raise ValueError(f"WithMeshHealth: nodes needs one entry per host ({num_nodes}), got {len(mh['nodes'])}")
         flags = 0
         if score is not None:
             flags |= _abi.GS_FLAG_SCORING
@@ -432,6 +449,19 @@ class Engine:
                                      _ptr(mask, C.c_uint8), 1 if insp["extended"] else 0)
             _check(lib, lib.gs_set_score_inspect(h, C.byref(ic)))
             self._inspect = dict(insp, bounds=bounds, mask=mask, delivered=0)
+        # include/gs_mesh_health.h: exported by the product library only
+        self._has_mesh_health = all(hasattr(self.lib, name) for name, _, _ in _abi.MESH_HEALTH_FUNCTIONS)
+        if self._has_mesh_health:
+            for name, res, args in _abi.MESH_HEALTH_FUNCTIONS:
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = res, args
+        if mh is not None:
+            if not self._has_mesh_health:
+                self.close()
+            lib = self._mesh_health_lib()
+            mask = np.ascontiguousarray(np.asarray(mh["nodes"]) != 0, dtype=np.uint8) if mh["nodes"] is not None else None
+            mc = _abi.MeshHealthConfigC(mh["period_hops"], mh["ticks"], _ptr(mask, C.c_uint8), 1 if mh["labels"] else 0)
+            _check(lib, lib.gs_set_mesh_health(h, C.byref(mc)))
         acct = opts.get("rpc_acct")
         if acct is not None:
             ms, idl, tl, pid, rec = acct
@@ -453,6 +483,7 @@ class Engine:
         # the schedule by message id (publish() appends): author, topic, hop
         self.msg_src, self.msg_topic = np.empty(0, np.int32), np.empty(0, np.int32)
         self.msg_hop = np.empty(0, np.int64)
+        self.events = []  # the events scheduled by schedule_events(): (hop, kind, a, b)
         self.edge_range = (int(self.rowptr[b.value]), int(self.rowptr[e.value]))
         subs = np.ascontiguousarray(subscriptions, dtype=np.uint64)
         _check(self.lib, self.lib.gs_set_subscriptions(h, _ptr(subs, C.c_uint64)))
@@ -515,6 +546,7 @@ class Engine:
         hop = np.ascontiguousarray(hop, dtype=np.int64)
         _check(self.lib, self.lib.gs_schedule_events(self.h, len(kind), _ptr(kind, C.c_int32), _ptr(a, C.c_int32),
                                                      _ptr(b, C.c_int32), _ptr(hop, C.c_int64)))
+        self.events += list(zip(hop.tolist(), kind.tolist(), a.tolist(), b.tolist()))
 
     def exchange_stats(self):
         """(host ms spent in the transport, bytes received from other ranks)."""
@@ -806,6 +838,53 @@ class Engine:
             k = st["delivered"]
             st["delivered"] += 1
             st["inspect"]((k + 1) * st["period_hops"], self._inspect_maps(k, edges))
+
+    # ---------------------------------------------------------------- mesh health
+    def _mesh_health_lib(self):
+        if not self._has_mesh_health:
+            raise ValueError("mesh health (WithMeshHealth): product library only")
+        return self.lib
+
+    def mesh_health_ticks(self):
+        """Ticks taken so far (gs_mesh_health_ticks)."""
+        lib = self._mesh_health_lib()
+        n = lib.gs_mesh_health_ticks(self.h)
+        if n < 0:
+            _check(lib, int(n))
+        return int(n)
+
+    def mesh_health_row(self, k):
+        """Tick k: dict(hop; members, components, largest, isolated, one_sided,
+        outside, eclipsed int64 [T]; comp_hist int64 [T, 32]) (gs_read_mesh_health_row)."""
+        lib = self._mesh_health_lib()
+        hop = C.c_int64()
+        row = np.zeros((self.T, len(_abi.MESH_ROW_FIELDS)), dtype=np.int64)
+        hist = np.zeros((self.T, _abi.GS_MESH_SIZE_BINS), dtype=np.int64)
+        _check(lib, lib.gs_read_mesh_health_row(self.h, int(k), C.byref(hop), _ptr(row, C.c_int64),
+                                                _ptr(hist, C.c_int64)))
+        out = {name: np.ascontiguousarray(row[:, i]) for i, name in enumerate(_abi.MESH_ROW_FIELDS)}
+        return dict(out, hop=hop.value, comp_hist=hist)
+
+    def mesh_labels(self):
+        """(tick, int32 [N, T]): the newest tick and every host's component label
+        per topic, the smallest host id of its component, -1 for a non-member
+        (WithMeshHealth(labels=True))."""
+        lib = self._mesh_health_lib()
+        tick = C.c_int64()
+        lab = np.zeros((self.N, self.T), dtype=np.int32)
+        _check(lib, lib.gs_read_mesh_labels(self.h, C.byref(tick), _ptr(lab, C.c_int32)))
+        return tick.value, lab
+
+    def mesh_health_kernel_stats(self):
+        """{"mesh_init" | "mesh_label" | "mesh_sizes" | "mesh_row": (total_ms,
+        launches)} since set_profiling(True), and "iterations" / "bytes": the
+        label iterations run and the bytes moved since then (or the start)."""
+        lib = self._mesh_health_lib()
+        ms = np.zeros(len(_abi.MESH_STAT_NAMES), dtype=np.float64)
+        cnt = np.zeros(len(_abi.MESH_STAT_NAMES), dtype=np.int64)
+        _check(lib, lib.gs_read_mesh_health_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
+        out = {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.MESH_KERNEL_NAMES)}
+        return dict(out, iterations=int(cnt[4]), bytes=int(cnt[5]))
 
     def deliveries(self, msg_id):
         hop = np.empty(self.N, dtype=np.int32)
