@@ -27,6 +27,7 @@
 #include "../../include/gs_latency.h"
 #include "../../include/gs_inspect.h"
 #include "../../include/gs_mesh_health.h"
+#include "../../include/gs_mesh_reach.h"
 #include "../../include/gs_window.h"
 #include "gs_window_layout.h"
 #include "gs_host.h"
@@ -35,6 +36,7 @@
 #include "gs_kernels_lat.h"
 #include "gs_kernels_insp.h"
 #include "gs_kernels_mesh.h"
+#include "gs_kernels_reach.h"
 #include "gs_exchange.h"
 
 #define HIPCHECK(expr)                                                        \
@@ -437,6 +439,21 @@ struct gs_engine {
   unsigned long long *dMeshRows = nullptr, *dMeshWords = nullptr;
   unsigned meshGrid = 0;
   int64_t meshIters = 0, meshBytes = 0;  // since the start or the last gs_set_profiling
+  // mesh reach (gs_mesh_reach.h): the two bit tables (uint64 [N][T]), a ring of
+  // reachCap rows (reach_row_len), the members per topic, the batch's flags,
+  // the byte counters and, when asked for, the depth table (uint8 [K][N][T])
+  bool reachOn = false, reachDepths = false;
+  int64_t reachPeriod = 0, reachTaken = 0;
+  int reachCap = 0;
+  std::vector<int32_t> reachSrc;      // [K] the sources
+  std::vector<uint8_t> reachMask;     // [N] the hosts that can be targets, or empty for all
+  int32_t* dReachSrc = nullptr;
+  uint8_t *dReachMask = nullptr, *dReachDepths = nullptr;
+  uint64_t* dReachR[2] = {nullptr, nullptr};
+  uint32_t *dReachMembers = nullptr, *dReachFlag = nullptr;  // flags: [GS_REACH_BATCH + 1]
+  unsigned long long *dReachRows = nullptr, *dReachWords = nullptr;
+  unsigned reachGrid = 0;
+  int64_t reachPasses = 0, reachLevels = 0, reachBytes = 0;  // since the start or the last gs_set_profiling
   // kernel timing: (kernel id, start event, end event) pending until a sync
   bool profiling = false;
   std::vector<hipEvent_t> evPool;
@@ -444,11 +461,12 @@ struct gs_engine {
   std::vector<int> pendKid;
   // (past the public kernel ids: the latency kernels, gs_read_latency_kernel_stats, and the
   // inspection's three passes, gs_read_inspect_kernel_stats; mesh health's four,
-  // gs_read_mesh_health_kernel_stats)
+  // gs_read_mesh_health_kernel_stats; mesh reach's four, gs_read_mesh_reach_kernel_stats)
   static constexpr int kLatCount = GS_NUM_KERNELS, kLatFold = GS_NUM_KERNELS + 1;
   static constexpr int kInspScore = GS_NUM_KERNELS + 2, kInspReduce = GS_NUM_KERNELS + 3;
   static constexpr int kInspGather = GS_NUM_KERNELS + 4, kMeshInit = GS_NUM_KERNELS + 5;
-  static constexpr int kTimed = kMeshInit + 4;  // (kMeshInit + GS_MESH_K_*)
+  static constexpr int kReachMembers = kMeshInit + 4;  // (kMeshInit + GS_MESH_K_*)
+  static constexpr int kTimed = kReachMembers + 4;     // (kReachMembers + GS_REACH_K_*)
   double kMs[kTimed] = {0};
   int64_t kLaunches[kTimed] = {0};
   hipEvent_t nextEvent() {
@@ -545,6 +563,12 @@ struct gs_engine {
     dMeshL = dMeshZ = dMeshFlag = nullptr;
     dMeshRows = dMeshWords = nullptr;
     meshTaken = 0;
+    dReachSrc = nullptr;
+    dReachMask = dReachDepths = nullptr;
+    dReachR[0] = dReachR[1] = nullptr;
+    dReachMembers = dReachFlag = nullptr;
+    dReachRows = dReachWords = nullptr;
+    reachTaken = 0;
     started = churnOn = allocFailed = false;
     uploaded = 0;
     aliveH.clear();
@@ -617,6 +641,7 @@ struct gs_engine {
   int allocLatency(), latencyStats(const Hop& hp);
   int allocInspect(), inspectTick();
   int allocMeshHealth(), meshTick();
+  int allocMeshReach(), reachTick();
   void refreshOrFold(const Hop& hp), heartbeat(const Hop& hp);
   template <bool ADV>
   PhaseADev<ADV> phaseADev() const {

@@ -178,6 +178,7 @@ int gs_engine::buildDevice(const Plan& pl) {
   GS_TRY(allocLatency());
   GS_TRY(allocInspect());
   GS_TRY(allocMeshHealth());
+  GS_TRY(allocMeshReach());
   GS_TRY(allocFail("state", "; reduce num_nodes or slots_per_topic"));
   GS_TRY(initConnections(pl));
   GS_TRY(allocAcct(pl));
@@ -823,6 +824,114 @@ int gs_engine::meshTick() {
   return GS_OK;
 }
 
+// Mesh reach (gs_mesh_reach.h) at its exact sizes: the two bit tables, the ring
+// of rows, the sources, the include mask, the members per topic, a batch's
+// flags, the byte counters and, when asked for, the depth table; the grid of
+// the node passes (mesh health's).
+int gs_engine::allocMeshReach() {
+  if (!reachOn) return GS_OK;
+  const size_t nt = (size_t)N * (size_t)T, K = reachSrc.size();
+  const bool before = allocFailed;
+  allocFailed = false;
+  dReachR[0] = dalloc<uint64_t>(nt);
+  dReachR[1] = dalloc<uint64_t>(nt);
+  dReachRows = dalloc<unsigned long long>((size_t)reachCap * (size_t)reach_row_len((int)K, T));
+  dReachSrc = dalloc<int32_t>(K);
+  dReachMembers = dalloc<uint32_t>((size_t)T);
+  dReachFlag = dalloc<uint32_t>(GS_REACH_BATCH + 1);
+  dReachWords = dalloc<unsigned long long>(GS_REACH_W_NUM);
+  if (!reachMask.empty()) dReachMask = dalloc<uint8_t>((size_t)N);
+  if (reachDepths) dReachDepths = dalloc<uint8_t>(K * nt, 0xFF);
+  if (allocFailed) return allocFail("mesh reach tables", "; reduce ticks, num_sources or num_nodes, or drop depths");
+  allocFailed = before;
+  GS_TRY(put(dReachSrc, reachSrc.data(), K));
+  GS_TRY(putNow(dReachMask, reachMask.data(), reachMask.size()));
+  int cus = 0;
+  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
+  reachGrid = std::min<unsigned>(GS_MESH_WGS_PER_CU * (unsigned)std::max(cus, 1),
+                                 std::max(nblk(mesh_groups(N, T), GS_MESH_BLOCK / 64), 1u));
+  return GS_OK;
+}
+
+// A tick at the end of a hop (`hop` already counts it), after the other
+// inspectors': the members once, then a pass per 64 sources.  A pass clears R0,
+// sets its sources' bits and runs the levels in batches of GS_REACH_BATCH,
+// level L reading R[(L - 1) & 1] and writing R[L & 1]; the host reads the
+// batch's flags in between (flag[i] != 0: level i of the batch ran; the last
+// flag 0: the level before set nothing, the search has ended), at most N levels
+// per pass.  The byte count: what every kernel streams, from the shapes, plus
+// what the level kernel counted.
+int gs_engine::reachTick() {
+  const int K = (int)reachSrc.size();
+  const int64_t nt = (int64_t)N * T;
+  unsigned long long* row = dReachRows + (size_t)(reachTaken % reachCap) * (size_t)reach_row_len(K, T);
+  unsigned long long* hist = row + (size_t)K * T * GS_REACH_ROW_FIELDS;
+  const bool wide = mesh_tp(T) == 64;
+  HIPCHECK(hipMemsetAsync(row, 0, (size_t)reach_row_len(K, T) * 8, stream));
+  HIPCHECK(hipMemsetAsync(dReachWords, 0, GS_REACH_W_NUM * 8, stream));
+  HIPCHECK(hipMemsetAsync(dReachMembers, 0, (size_t)T * 4, stream));
+  if (reachDepths) HIPCHECK(hipMemsetAsync(dReachDepths, 0xFF, (size_t)K * (size_t)nt, stream));
+  TIMED(this, kReachMembers + GS_REACH_K_MEMBERS,
+        (k_reach_members<<<reachGrid, GS_MESH_BLOCK, 0, stream>>>(d, dReachMask, dReachMembers)));
+  int64_t levels = 0;
+  int passes = 0;
+  for (int k0 = 0; k0 < K; k0 += 64, ++passes) {
+    const int ns = std::min(64, K - k0);
+    const uint64_t full = ns == 64 ? ~0ull : (1ull << ns) - 1ull;
+    unsigned long long* prow = row + (size_t)k0 * T * GS_REACH_ROW_FIELDS;
+    unsigned long long* phist = hist + (size_t)k0 * T * GS_REACH_DEPTH_BINS;
+    uint8_t* pdepths = reachDepths ? dReachDepths + (size_t)k0 * (size_t)nt : nullptr;
+    HIPCHECK(hipMemsetAsync(dReachR[0], 0, (size_t)nt * 8, stream));
+    TIMED(this, kReachMembers + GS_REACH_K_INIT,
+          (k_reach_init<<<nblk((int64_t)ns * T, 256), 256, 0, stream>>>(d, dReachSrc + k0, ns, dReachR[0], pdepths)));
+    int64_t ran = 0;
+    for (bool ended = false; !ended;) {
+      const int n = (int)std::min<int64_t>(GS_REACH_BATCH, (int64_t)N - ran);
+      if (n <= 0) {
+        gs_set_error("mesh reach: levels did not end after " + std::to_string(ran) + " (hop " + std::to_string(hop) +
+                     ")");
+        return GS_EDEVICE;
+      }
+      HIPCHECK(hipMemsetAsync(dReachFlag, 0, (size_t)(GS_REACH_BATCH + 1) * 4, stream));
+      HIPCHECK(hipMemsetAsync(dReachFlag, 1, 4, stream));  // non-zero: the batch's first level runs
+      for (int i = 0; i < n; ++i) {
+        const int level = (int)ran + i + 1;  // (a launch past the search's end returns at once: its level is not used)
+        with_consts([&](auto w) {
+          TIMED(this, kReachMembers + GS_REACH_K_LEVEL,
+                (k_reach_level<CV(w)><<<reachGrid, GS_MESH_BLOCK, 0, stream>>>(
+                    d, dReachMask, dReachR[(level - 1) & 1], dReachR[level & 1], full, level, dReachFlag + i, prow,
+                    phist, pdepths, dReachWords)));
+        }, Flag{wide});
+      }
+      uint32_t flag[GS_REACH_BATCH + 1];
+      HIPCHECK(hipMemcpyAsync(flag, dReachFlag, sizeof flag, hipMemcpyDeviceToHost, stream));
+      HIPCHECK(hipStreamSynchronize(stream));
+      for (int i = 0; i < n; ++i) ran += flag[i] != 0u;
+      ended = flag[n] == 0u;
+    }
+    TIMED(this, kReachMembers + GS_REACH_K_FINISH,
+          (k_reach_finish<<<nblk((int64_t)ns * T, 256), 256, 0, stream>>>(d, dReachMask, dReachSrc + k0, ns,
+                                                                           dReachMembers, prow)));
+    levels += ran;
+  }
+  HIPCHECK(hipGetLastError());
+  unsigned long long words[GS_REACH_W_NUM];
+  HIPCHECK(hipMemcpyAsync(words, dReachWords, sizeof words, hipMemcpyDeviceToHost, stream));
+  HIPCHECK(hipStreamSynchronize(stream));
+  reachPasses += passes;
+  reachLevels += levels;
+  reachBytes += (int64_t)N * 10                                   // members: the subscription word, router and include bytes
+                + (reachDepths ? (int64_t)K * nt : 0)             // the depth table's fill
+                + passes * nt * 8 + (int64_t)K * T * (4 + 8)      // a pass's cleared table, its sources' words
+                + levels * (nt * 16 + (int64_t)N * (10 + 8))      // a level: both tables, the member test, the CSR row bounds
+                + (int64_t)words[GS_REACH_W_GATHER] * 8           // the neighbours' words gathered
+                + (int64_t)words[GS_REACH_W_EDGES] * (8 + 8 + 4 + 4)  // per edge walked: mesh and fanout of the reverse edge, it, the peer
+                + (int64_t)words[GS_REACH_W_DEPTHS]               // depth bytes stored
+                + (int64_t)K * T * (GS_REACH_ROW_T + 1) * 8;      // the row: cleared, UNREACHED
+  reachTaken++;
+  return GS_OK;
+}
+
 int gs_engine::allocTrace() {
   Dev& x = d;
   if (traceMask.empty()) return GS_OK;
@@ -1187,6 +1296,7 @@ int gs_engine::stepOne() {
   hop++;
   if (inspOn && hop % inspPeriod == 0) GS_TRY(inspectTick());
   if (meshOn && hop % meshPeriod == 0) GS_TRY(meshTick());
+  if (reachOn && hop % reachPeriod == 0) GS_TRY(reachTick());
   return GS_OK;
 }
 
@@ -2236,6 +2346,7 @@ int gs_set_partition(gs_engine* g, int32_t rank, int32_t world, const gs_transpo
   if (g->started) { gs_set_error("the partition must be set before the first step"); return GS_ESTATE; }
   if (world < 1 || world > 255 || rank < 0 || rank >= world) { gs_set_error("bad rank / world"); return GS_EINVAL; }
   if (world > 1 && g->meshOn) { gs_set_error("mesh health: not on a partitioned engine"); return GS_EUNSUPPORTED; }
+  if (world > 1 && g->reachOn) { gs_set_error("mesh reach: not on a partitioned engine"); return GS_EUNSUPPORTED; }
   if (world > 1 && (!tr || !tr->allgather_i64 || !tr->allgather || !tr->alltoallv)) {
     gs_set_error("a partitioned engine needs a transport with allgather_i64, allgather and alltoallv");
     return GS_EINVAL;
@@ -2857,6 +2968,105 @@ int gs_read_mesh_health_kernel_stats(gs_engine* g, double* total_ms, int64_t* la
   return GS_OK;
 }
 
+// ---- mesh reach (include/gs_mesh_reach.h)
+int gs_set_mesh_reach(gs_engine* g, const gs_mesh_reach_config* c) {
+  if (g->started) { gs_set_error("the mesh reach inspector must be set before the first step"); return GS_ESTATE; }
+  if (g->reachOn) { gs_set_error("duplicate mesh reach inspector"); return GS_ESTATE; }
+  if (g->cfg.router != GS_ROUTER_GOSSIPSUB) { gs_set_error("pubsub router is not gossipsub"); return GS_EUNSUPPORTED; }
+  if (g->world > 1) { gs_set_error("mesh reach: not on a partitioned engine"); return GS_EUNSUPPORTED; }
+  if (!c || c->period_hops <= 0) { gs_set_error("mesh reach: period_hops must be positive"); return GS_EINVAL; }
+  if (c->ticks < 1) { gs_set_error("mesh reach: ticks must be at least 1"); return GS_EINVAL; }
+  if (c->num_sources < 1 || c->num_sources > GS_REACH_MAX_SOURCES) {
+    gs_set_error("mesh reach: num_sources must be 1 .. " + std::to_string(GS_REACH_MAX_SOURCES));
+    return GS_EINVAL;
+  }
+  if (!c->sources) { gs_set_error("mesh reach: no sources given"); return GS_EINVAL; }
+  std::vector<int32_t> src(c->sources, c->sources + c->num_sources), sorted(src);
+  std::sort(sorted.begin(), sorted.end());
+  if (sorted.front() < 0 || sorted.back() >= g->N) {
+    gs_set_error("mesh reach: a source is outside 0 .. " + std::to_string(g->N - 1));
+    return GS_EINVAL;
+  }
+  const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+  if (dup != sorted.end()) {
+    gs_set_error("mesh reach: source " + std::to_string(*dup) + " is given twice");
+    return GS_EINVAL;
+  }
+  g->reachPeriod = c->period_hops;
+  g->reachCap = c->ticks;
+  g->reachSrc = std::move(src);
+  g->reachMask.clear();
+  if (c->include) g->reachMask.assign(c->include, c->include + g->N);
+  g->reachDepths = c->depths != 0;
+  g->reachOn = true;
+  return GS_OK;
+}
+
+static int reach_on(const gs_engine* g) {
+  if (!g->reachOn) { gs_set_error("mesh reach is off (gs_set_mesh_reach)"); return GS_ESTATE; }
+  return GS_OK;
+}
+
+int64_t gs_mesh_reach_ticks(const gs_engine* g) {
+  GS_TRY(reach_on(g));
+  return g->reachTaken;
+}
+
+// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
+int gs_read_mesh_reach_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* row, int64_t* depth_hist) {
+  GS_TRY(reach_on(g));
+  if (tick < 0 || tick >= g->reachTaken) {
+    gs_set_error("mesh reach: tick " + std::to_string(tick) + " not taken yet (" + std::to_string(g->reachTaken) +
+                 " so far)");
+    return GS_EINVAL;
+  }
+  if (tick < g->reachTaken - g->reachCap) {
+    gs_set_error("mesh reach: tick " + std::to_string(tick) + " already overwritten (ring of " +
+                 std::to_string(g->reachCap) + ")");
+    return GS_ESTATE;
+  }
+  if (hop) *hop = (tick + 1) * g->reachPeriod;
+  const int K = (int)g->reachSrc.size();
+  const size_t nf = (size_t)K * g->T * GS_REACH_ROW_FIELDS;
+  const unsigned long long* src = g->dReachRows + (size_t)(tick % g->reachCap) * (size_t)reach_row_len(K, g->T);
+  if (row) HIPCHECK(hipMemcpyAsync(row, src, nf * 8, hipMemcpyDeviceToHost, g->stream));
+  if (depth_hist)
+    HIPCHECK(hipMemcpyAsync(depth_hist, src + nf, (size_t)K * g->T * GS_REACH_DEPTH_BINS * 8, hipMemcpyDeviceToHost,
+                            g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+// The depth table is the newest tick's until the next tick starts over.
+int gs_read_mesh_reach_depths(gs_engine* g, int64_t* tick, uint8_t* depths) {
+  GS_TRY(reach_on(g));
+  if (!g->reachDepths) { gs_set_error("mesh reach: the depth table is not kept (depths = 0)"); return GS_ESTATE; }
+  if (g->reachTaken == 0) { gs_set_error("mesh reach: no tick taken yet"); return GS_EINVAL; }
+  if (tick) *tick = g->reachTaken - 1;
+  if (depths)
+    HIPCHECK(hipMemcpyAsync(depths, g->dReachDepths, g->reachSrc.size() * (size_t)g->N * (size_t)g->T,
+                            hipMemcpyDeviceToHost, g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_mesh_reach_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
+  GS_TRY(reach_on(g));
+  if (g->started) {
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    g->resolveTimings();
+  }
+  for (int i = 0; i < GS_REACH_ST_PASSES; ++i) {
+    total_ms[i] = g->kMs[gs_engine::kReachMembers + i];
+    launches[i] = g->kLaunches[gs_engine::kReachMembers + i];
+  }
+  total_ms[GS_REACH_ST_PASSES] = total_ms[GS_REACH_ST_LEVELS] = total_ms[GS_REACH_ST_BYTES] = 0.0;
+  launches[GS_REACH_ST_PASSES] = g->reachPasses;
+  launches[GS_REACH_ST_LEVELS] = g->reachLevels;
+  launches[GS_REACH_ST_BYTES] = g->reachBytes;
+  return GS_OK;
+}
+
 #ifdef GS_STAMPS
 // Debug build: phase-A cycle stamps of the sampled nodes of the last hop.
 int gs_debug_stamps(gs_engine* g, unsigned long long* out, int n) {
@@ -2880,6 +3090,7 @@ int gs_set_profiling(gs_engine* g, int on) {
   g->profiling = on != 0;
   for (int i = 0; i < gs_engine::kTimed; ++i) { g->kMs[i] = 0; g->kLaunches[i] = 0; }
   g->meshIters = g->meshBytes = 0;
+  g->reachPasses = g->reachLevels = g->reachBytes = 0;
   return GS_OK;
 }
 

@@ -18,5 +18,5 @@ from .engine import (PRODUCT_LIB, Engine, GossipEngineError, NewFloodSub, NewGos
                      WithHop, WithMessageWindow, WithPartition, WithPeerScore, WithPeertxCapacity, WithFrontierLists, WithFrontierBitmaps, WithRecordDeliveries, WithSeed,
                      WithBehaviour, WithPeerGater, WithRPCAccounting, WithValidation, WithPeerExchange, WithDormant,
                      WithRouters, WithProtocols, WithIPWhitelist, WithLatencyStats, WithTopicWindows, latency_quantiles,
-                     WithMeshHealth, WithPeerScoreInspect, PeerScoreSnapshot, TopicScoreSnapshot, default_inspect_bounds,
+                     WithMeshHealth, WithMeshReach, WithPeerScoreInspect, PeerScoreSnapshot, TopicScoreSnapshot, default_inspect_bounds,
                      load)

@@ -278,6 +278,28 @@ MESH_HEALTH_FUNCTIONS = [
 MESH_KERNEL_NAMES = ["mesh_init", "mesh_label", "mesh_sizes", "mesh_row"]
 MESH_STAT_NAMES = MESH_KERNEL_NAMES + ["iterations", "bytes"]
 
+# include/gs_mesh_reach.h (product library only; bound by Engine with WithMeshReach)
+GS_REACH_DEPTH_BINS = 64
+GS_REACH_MAX_SOURCES = 256
+REACH_ROW_FIELDS = ["reached", "unreached", "ecc"]
+
+
+class MeshReachConfigC(C.Structure):
+    _fields_ = [("period_hops", i64), ("ticks", i32), ("num_sources", i32), ("sources", C.POINTER(i32)),
+                ("include", C.POINTER(u8)), ("depths", i32)]
+
+
+MESH_REACH_FUNCTIONS = [
+    ("gs_set_mesh_reach", C.c_int, [P, C.POINTER(MeshReachConfigC)]),
+    ("gs_mesh_reach_ticks", i64, [P]),
+    ("gs_read_mesh_reach_row", C.c_int, [P, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    ("gs_read_mesh_reach_depths", C.c_int, [P, C.POINTER(i64), C.POINTER(u8)]),
+    ("gs_read_mesh_reach_kernel_stats", C.c_int, [P, C.POINTER(f64), C.POINTER(i64)]),
+]
+# the four kernels (total_ms, launches), then three counts
+REACH_KERNEL_NAMES = ["reach_members", "reach_init", "reach_level", "reach_finish"]
+REACH_STAT_NAMES = REACH_KERNEL_NAMES + ["passes", "levels", "bytes"]
+
 KERNEL_NAMES = ["score", "refresh", "join", "fanout", "fwd", "phase_a", "publish", "phase_b",
                 "hb_pre", "heartbeat", "push"]
 

@@ -305,6 +305,29 @@ def WithMeshHealth(period, *, nodes=None, ticks=64, labels=False):
     return ("mesh_health", dict(period=int(period), nodes=nodes, ticks=int(ticks), labels=bool(labels)))
 
 
+def WithMeshReach(period, sources, *, nodes=None, ticks=64, depths=False):
+    """Mesh reach (include/gs_mesh_reach.h, product library only): every
+    `period` (ns, a positive multiple of the hop) the engine searches, inside
+    step(), breadth first from each host of `sources` (distinct host ids, at
+    most 256) over every topic's eager-push edges (mesh | fanout) through the
+    member hosts of `nodes` (a bool or byte mask over the hosts; None: all), and
+    counts the targets reached, not reached, the largest depth and the targets
+    per depth into a ring of `ticks` ticks; depths=True keeps the newest tick's
+    depth per (source, host, topic) readable.  Read with Engine.mesh_reach_row(),
+    mesh_reach_depths().  Not on a partitioned engine."""
+    if int(ticks) < 1:
+        raise ValueError("WithMeshReach: ticks must be at least 1")
+    src = np.asarray(sources)
+    if src.ndim != 1 or not 1 <= len(src) <= _abi.GS_REACH_MAX_SOURCES:
+        raise ValueError(f"WithMeshReach: sources must be 1 .. {_abi.GS_REACH_MAX_SOURCES} host ids")
+    if src.dtype.kind not in "iu":
+        raise ValueError("WithMeshReach: sources must be host ids (integers)")
+    if len(np.unique(src)) != len(src):
+        raise ValueError("WithMeshReach: a source is given twice")
+    return ("mesh_reach", dict(period=int(period), sources=src.astype(np.int64), nodes=nodes, ticks=int(ticks),
+                               depths=bool(depths)))
+
+
 def WithPartition(rank, world, transport):
     """Simulate only this rank's node range; exchange RPCs with the other
     ranks through `transport` (a pubsub_amd.transport.TorchTransport) once per
@@ -337,6 +360,13 @@ class Engine:
             mh = dict(mh, period_hops=_inspect_period_hops(mh["period"], cfg.hop_ns, "WithMeshHealth"))
             if mh["nodes"] is not None and len(mh["nodes"]) != num_nodes:
                 raise ValueError(f"WithMeshHealth: nodes needs one entry per host ({num_nodes}), got {len(mh['nodes'])}")
+        mr = opts.get("mesh_reach")
+        if mr is not None:
+            mr = dict(mr, period_hops=_inspect_period_hops(mr["period"], cfg.hop_ns, "WithMeshReach"))
+            if mr["nodes"] is not None and len(mr["nodes"]) != num_nodes:
+                raise ValueError(f"WithMeshReach: nodes needs one entry per host ({num_nodes}), got {len(mr['nodes'])}")
+            if mr["sources"].min() < 0 or mr["sources"].max() >= num_nodes:
+                raise ValueError(f"WithMeshReach: a source is outside 0 .. {num_nodes - 1}")
         flags = 0
         if score is not None:
             flags |= _abi.GS_FLAG_SCORING
@@ -462,6 +492,23 @@ class Engine:
             mask = np.ascontiguousarray(np.asarray(mh["nodes"]) != 0, dtype=np.uint8) if mh["nodes"] is not None else None
             mc = _abi.MeshHealthConfigC(mh["period_hops"], mh["ticks"], _ptr(mask, C.c_uint8), 1 if mh["labels"] else 0)
             _check(lib, lib.gs_set_mesh_health(h, C.byref(mc)))
+        # include/gs_mesh_reach.h: exported by the product library only
+        self._has_mesh_reach = all(hasattr(self.lib, name) for name, _, _ in _abi.MESH_REACH_FUNCTIONS)
+        if self._has_mesh_reach:
+            for name, res, args in _abi.MESH_REACH_FUNCTIONS:
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = res, args
+        self._reach_sources = 0
+        if mr is not None:
+            if not self._has_mesh_reach:
+                self.close()
+            lib = self._mesh_reach_lib()
+            mask = np.ascontiguousarray(np.asarray(mr["nodes"]) != 0, dtype=np.uint8) if mr["nodes"] is not None else None
+            src = np.ascontiguousarray(mr["sources"], dtype=np.int32)
+            rc = _abi.MeshReachConfigC(mr["period_hops"], mr["ticks"], len(src), _ptr(src, C.c_int32),
+                                       _ptr(mask, C.c_uint8), 1 if mr["depths"] else 0)
+            _check(lib, lib.gs_set_mesh_reach(h, C.byref(rc)))
+            self._reach_sources = len(src)
         acct = opts.get("rpc_acct")
         if acct is not None:
             ms, idl, tl, pid, rec = acct
@@ -885,6 +932,55 @@ class Engine:
         _check(lib, lib.gs_read_mesh_health_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
         out = {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.MESH_KERNEL_NAMES)}
         return dict(out, iterations=int(cnt[4]), bytes=int(cnt[5]))
+
+    # ---------------------------------------------------------------- mesh reach
+    def _mesh_reach_lib(self):
+        if not self._has_mesh_reach:
+            raise ValueError("mesh reach (WithMeshReach): product library only")
+        return self.lib
+
+    def mesh_reach_ticks(self):
+        """Ticks taken so far (gs_mesh_reach_ticks)."""
+        lib = self._mesh_reach_lib()
+        n = lib.gs_mesh_reach_ticks(self.h)
+        if n < 0:
+            _check(lib, int(n))
+        return int(n)
+
+    def mesh_reach_row(self, k):
+        """Tick k: dict(hop; reached, unreached, ecc int64 [K, T]; depth_hist
+        int64 [K, T, 64]) over the K sources (gs_read_mesh_reach_row)."""
+        lib = self._mesh_reach_lib()
+        K = max(self._reach_sources, 1)
+        hop = C.c_int64()
+        row = np.zeros((K, self.T, len(_abi.REACH_ROW_FIELDS)), dtype=np.int64)
+        hist = np.zeros((K, self.T, _abi.GS_REACH_DEPTH_BINS), dtype=np.int64)
+        _check(lib, lib.gs_read_mesh_reach_row(self.h, int(k), C.byref(hop), _ptr(row, C.c_int64),
+                                               _ptr(hist, C.c_int64)))
+        out = {name: np.ascontiguousarray(row[:, :, i]) for i, name in enumerate(_abi.REACH_ROW_FIELDS)}
+        return dict(out, hop=hop.value, depth_hist=hist)
+
+    def mesh_reach_depths(self):
+        """(tick, uint8 [K, N, T]): the newest tick and every host's eager-push
+        depth from every source per topic: 0 in the source's own row, 255 where
+        it is not reached, depths past 254 read 254 (WithMeshReach(depths=True))."""
+        lib = self._mesh_reach_lib()
+        tick = C.c_int64()
+        dep = np.zeros((max(self._reach_sources, 1), self.N, self.T), dtype=np.uint8)
+        _check(lib, lib.gs_read_mesh_reach_depths(self.h, C.byref(tick), _ptr(dep, C.c_uint8)))
+        return tick.value, dep
+
+    def mesh_reach_kernel_stats(self):
+        """{"reach_members" | "reach_init" | "reach_level" | "reach_finish":
+        (total_ms, launches)} since set_profiling(True), and "passes" / "levels"
+        / "bytes": the passes and levels run and the bytes moved since then (or
+        the start)."""
+        lib = self._mesh_reach_lib()
+        ms = np.zeros(len(_abi.REACH_STAT_NAMES), dtype=np.float64)
+        cnt = np.zeros(len(_abi.REACH_STAT_NAMES), dtype=np.int64)
+        _check(lib, lib.gs_read_mesh_reach_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
+        out = {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.REACH_KERNEL_NAMES)}
+        return dict(out, passes=int(cnt[4]), levels=int(cnt[5]), bytes=int(cnt[6]))
 
     def deliveries(self, msg_id):
         hop = np.empty(self.N, dtype=np.int32)
