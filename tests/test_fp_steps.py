@@ -1,7 +1,9 @@
 """include/gs_fp.h: gs_add_ones / gs_add_ones_capped (the engine's +1-step
 counter updates, one exact add per binade) equal the reference's one-step-at-
 a-time `x += 1` bit for bit (CPU: compiled with g++ against a serial loop on
-decayed fractional counters, binade crossings, caps, large n)."""
+decayed fractional counters, binade crossings, caps, large n).  The device
+compilation of the header, gs_quantum_div's __umul64hi branch included, is
+checked on the same case families by tests/test_device_shared_headers_gpu.py."""
 import os
 import subprocess
 
