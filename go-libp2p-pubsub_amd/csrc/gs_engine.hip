@@ -521,6 +521,21 @@ int gs_engine::allocNodeTables(const Plan& pl) {
   const bool spamRun = (behaveAll & GS_BEHAVE_IWANT_SPAM) != 0;
   x.ptxBits = ptxHomeBits >= 0 ? ptxHomeBits : (spamRun ? 12 : GS_PTX_BITS);
   x.ptxOBits = ptxOvfBits >= 0 ? ptxOvfBits : (spamRun ? 20 : 16);
+  {
+    // the heartbeat's rebuild stages a node's whole table in LDS: refuse here
+    // what the device cannot hold instead of failing that launch
+    int lim = 0;
+    hipFuncAttributes fa{};
+    HIPCHECK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg.device));
+    HIPCHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_ptx_rebuild)));
+    const size_t need = ptx_rebuild_lds(x.ptxBits) + fa.sharedSizeBytes;
+    if (need > (size_t)lim) {
+      gs_set_error("gs_set_peertx_capacity: home_bits " + std::to_string(x.ptxBits) + " needs " + std::to_string(need) +
+                   " bytes of LDS per workgroup for the heartbeat's peertx rebuild, the device has " +
+                   std::to_string(lim) + ": lower home_bits");
+      return GS_ECAPACITY;
+    }
+  }
   x.ptxT = nalloc<uint32_t>((size_t)1 << x.ptxBits);
   x.ptxN = nalloc<int32_t>(1);
   x.ptxO = dalloc<unsigned long long>((size_t)1 << x.ptxOBits);
@@ -1552,13 +1567,7 @@ void gs_engine::heartbeat(const Hop& hp) {
             k_heartbeat<CV(half)><<<no, 64, 0, stream>>>(d, h, now, ticks, hp.cur, head, newhead);
           }, Flag{d.maxDeg <= 32}));
   // the peertx counters of the window that left the cache (pre-shift HL - 1)
-  if (no) {
-    k_ptx_rebuild<<<no, 64, (size_t)4 << d.ptxBits, stream>>>(d, (head + d.HL - 1) % R);
-    const int64_t nO = (int64_t)1 << d.ptxOBits;  // (a table without entries returns at once)
-    k_ptxo_collect<<<nblk(nO, 256), 256, 0, stream>>>(d, (head + d.HL - 1) % R);
-    k_ptxo_reinsert<<<nblk(nO, 256), 256, 0, stream>>>(d);
-    k_ptxo_fin<<<1, 1, 0, stream>>>(d);
-  }
+  if (no) ptx_rebuild_launch(d, no, (head + d.HL - 1) % R, stream);
   head = newhead;
   heartbeats++;
 }

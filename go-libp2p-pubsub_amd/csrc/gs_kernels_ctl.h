@@ -2156,6 +2156,20 @@ __global__ void k_ptxo_fin(Dev d) {
   d.ptxOCnt[1] = 0u;
   d.ptxOCnt[2] = 0u;
 }
+// The four launches of the rebuild for `no` owned nodes (> 0), in order, with
+// the one geometry they are written for (the heartbeat and the test-only probe
+// both launch them through here).  ptx_rebuild_lds bytes of dynamic LDS must
+// fit the device's limit per workgroup: the host checks it where it sizes the
+// tables.
+inline size_t ptx_rebuild_lds(int ptxBits) { return (size_t)4 << ptxBits; }
+inline void ptx_rebuild_launch(const Dev& d, int no, int last, hipStream_t stream) {
+  k_ptx_rebuild<<<no, 64, ptx_rebuild_lds(d.ptxBits), stream>>>(d, last);
+  const int64_t nO = (int64_t)1 << d.ptxOBits;  // (a table without entries returns at once)
+  const unsigned gO = (unsigned)((nO + 255) / 256);
+  k_ptxo_collect<<<gO, 256, 0, stream>>>(d, last);
+  k_ptxo_reinsert<<<gO, 256, 0, stream>>>(d);
+  k_ptxo_fin<<<1, 1, 0, stream>>>(d);
+}
 
 // gs_read_deliveries gather
 __global__ void k_read_deliv(Dev d, int slot, int64_t pubhop, int32_t* hop, int32_t* from) {

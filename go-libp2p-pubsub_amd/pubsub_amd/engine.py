@@ -179,7 +179,9 @@ def WithIPWhitelist(nets):
 def WithPeertxCapacity(home_bits, overflow_bits):
     """mcache.peertx capacity (gs_set_peertx_capacity): 2^home_bits slots per
     node, and a per-rank overflow table of 2^overflow_bits entries for nodes
-    whose own table is full."""
+    whose own table is full.  A row must fit the device's LDS per workgroup
+    (4 << home_bits bytes: 15 at most on an MI355X), else the first step fails
+    with GS_ECAPACITY."""
     return ("peertx", (int(home_bits), int(overflow_bits)))
 
 

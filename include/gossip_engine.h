@@ -373,8 +373,13 @@ int gs_schedule_events(gs_engine* eng, int32_t n, const int32_t* kind, const int
  * (default 10; 12 with IWANT spammers, 2..16) and a per-rank overflow table of
  * 2^overflow_bits entries (default 16; 20 with IWANT spammers, 8..30) that takes
  * the keys of nodes whose own table is full.  Only a full overflow table is a
- * GS_ECAPACITY error of gs_step.  Replaces no reference call: the reference's
- * peertx is an unbounded Go map. */
+ * GS_ECAPACITY error of gs_step.  home_bits is bounded by the device, not by
+ * 16: every heartbeat rebuilds a node's table in LDS, 4 << home_bits bytes in
+ * one workgroup, and a size above the device's LDS per workgroup
+ * (hipDeviceAttributeMaxSharedMemoryPerBlock: 15 at most where it is 160 KiB,
+ * 14 where it is 64 KiB) is refused with GS_ECAPACITY at the first step,
+ * naming home_bits and both byte counts.  Replaces no reference call: the
+ * reference's peertx is an unbounded Go map. */
 int gs_set_peertx_capacity(gs_engine* eng, int32_t home_bits, int32_t overflow_bits);
 /* Before the first step: how phase A reads what the senders forwarded.
  * GS_FRONTIER_AUTO (default): frontier bitmaps where they measured faster

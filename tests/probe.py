@@ -32,7 +32,8 @@ def lib():
             raise ProbeError(f"{PROBE_LIB} is missing; build it with: {BUILD_HINT}")
         _lib = C.CDLL(PROBE_LIB, mode=C.RTLD_LOCAL)
         for name in ("gsp_consts", "gsp_select_k", "gsp_select_kth", "gsp_lanes", "gsp_item_sender", "gsp_dlt",
-                     "gsp_philox", "gsp_keys", "gsp_quantum_div", "gsp_add_ones", "gsp_ptx_hash", "gsp_peertx"):
+                     "gsp_philox", "gsp_keys", "gsp_quantum_div", "gsp_add_ones", "gsp_ptx_hash", "gsp_peertx",
+                     "gsp_lds_limit", "gsp_ptx_rebuild", "gsp_spam", "gsp_pool_take"):
             getattr(_lib, name).restype = C.c_int
     return _lib
 
@@ -55,12 +56,19 @@ def _call(name, *args):
 
 
 def consts():
-    """{'GS_SEL_WIN', 'GS_SEL_CAP', 'E_PEERTX'} as the device code was built."""
-    out = np.zeros(4, dtype=np.int32)
+    """{'GS_SEL_WIN', 'GS_SEL_CAP', 'E_PEERTX', 'E_POOL'} as the device code was built."""
+    out = np.zeros(5, dtype=np.int32)
     _call("gsp_consts", _p(out))
     if int(out[3]) != OP_COUNT:
         raise ProbeError("tests/probe.py and gs_probe.hip disagree on the gsp_lanes ops")
-    return {"GS_SEL_WIN": int(out[0]), "GS_SEL_CAP": int(out[1]), "E_PEERTX": int(out[2])}
+    return {"GS_SEL_WIN": int(out[0]), "GS_SEL_CAP": int(out[1]), "E_PEERTX": int(out[2]), "E_POOL": int(out[4])}
+
+
+def lds_limit():
+    """hipDeviceAttributeMaxSharedMemoryPerBlock of the current device, in bytes."""
+    out = np.zeros(1, dtype=np.int32)
+    _call("gsp_lds_limit", _p(out))
+    return int(out[0])
 
 
 def select_k(mode, cand, key, k):
@@ -172,6 +180,7 @@ class PeerTx:
         self.rows = np.zeros(n_nodes << bits, dtype=np.uint32)
         self.ovf = np.zeros(1 << obits, dtype=np.uint64)
         self.ocnt = np.zeros(3, dtype=np.uint32)
+        self.ptxn = np.zeros(n_nodes, dtype=np.int32)  # Dev::ptxN, kept as the engine keeps it
         self.err = np.zeros(1, dtype=np.int32)
 
     def run(self, rounds=(), queries=()):
@@ -194,4 +203,70 @@ class PeerTx:
               _p(self.rows), _p(self.ovf), _p(self.ocnt), _p(self.err), C.c_int(len(rounds)), C.c_int(per if rounds else 0),
               _p(node), _p(key), _p(ret), _p(ins), C.c_int(qn.size), _p(qn), _p(qk), _p(cg), _p(co))
         out = [(ret[i, :len(r)].copy(), ins[i, :len(r)].astype(bool)) for i, r in enumerate(rounds)]
+        for r, (_, inserted) in zip(rounds, out):  # handleIWant's pass: ptxN[v] += inserts (of either table)
+            for (v, _), i in zip(r, inserted):
+                self.ptxn[v] += int(i)
         return out, cg, co
+
+    def rebuild(self, hist, last):
+        """The heartbeat's rebuild, once: hist is the mcache ring [R][n_nodes][W]
+        of uint64 words, `last` the ring row of the window leaving the cache."""
+        hist = np.ascontiguousarray(hist, dtype=np.uint64)
+        r, n, w = hist.shape
+        if n != self.n_nodes:
+            raise ValueError("hist is [R][n_nodes][W]")
+        _call("gsp_ptx_rebuild", C.c_int(self.bits), C.c_int(self.obits), C.c_int(self.n_nodes), _p(self.rows),
+              _p(self.ptxn), _p(self.ovf), _p(self.ocnt), C.c_int(r), C.c_int(w), C.c_int(last), _p(hist))
+
+
+def spam(s, gr, cnt, rounds=(), retire=None):
+    """cnt: spamCnt [rows][s / 8] uint32, updated in place.  rounds: lists of
+    (row, slot) spam_incr calls run concurrently ((row, slot) distinct within a
+    round); returns the returned count of every call, per round.  retire: None,
+    or a dict for one launch of k_retire afterwards: cur, rowptr [nodes + 1],
+    spam_row [edges] or None, pubmask [s / 64], words, pmask_row [nodes] or
+    None, pmask [rows][s] uint64 (updated in place)."""
+    if cnt.dtype != np.uint32 or not cnt.flags.c_contiguous or cnt.ndim != 2 or cnt.shape[1] != s // 8:
+        raise ValueError("cnt is a contiguous uint32 array [rows][s / 8]")
+    per = max((len(r) for r in rounds), default=0)
+    row = np.full((len(rounds), max(per, 1)), -1, dtype=np.int32)
+    slot = np.zeros(row.shape, dtype=np.int32)
+    for i, r in enumerate(rounds):
+        for j, (a, b) in enumerate(r):
+            row[i, j], slot[i, j] = a, b
+    ret = np.zeros(row.shape, dtype=np.int32)
+    null = C.c_void_p(None)
+    if retire is None:
+        tail = (C.c_int(0), C.c_int(0), C.c_int(0), null, null, null, C.c_int(0), null, null, C.c_int(0), null)
+    else:
+        rowptr = _in(retire["rowptr"], np.int64)
+        n_nodes = rowptr.size - 1
+        spam_row = None if retire.get("spam_row") is None else _in(retire["spam_row"], np.int32, int(rowptr[-1]))
+        pubmask = _in(retire["pubmask"], np.uint64, s // 64)
+        words = _in(retire["words"], np.int32)
+        pmask_row = None if retire.get("pmask_row") is None else _in(retire["pmask_row"], np.int32, n_nodes)
+        pmask = retire.get("pmask")
+        n_pm = 0
+        if pmask_row is not None:
+            if pmask.dtype != np.uint64 or not pmask.flags.c_contiguous or pmask.ndim != 2 or pmask.shape[1] != s:
+                raise ValueError("pmask is a contiguous uint64 array [rows][s]")
+            n_pm = pmask.shape[0]
+        tail = (C.c_int(1), C.c_int(retire["cur"]), C.c_int(n_nodes), _p(rowptr), null if spam_row is None else _p(spam_row),
+                _p(pubmask), C.c_int(words.size), _p(words), null if pmask_row is None else _p(pmask_row), C.c_int(n_pm),
+                null if pmask_row is None else _p(pmask))
+    _call("gsp_spam", C.c_int(s), C.c_int(gr), C.c_int(cnt.shape[0]), _p(cnt), C.c_int(len(rounds)),
+          C.c_int(per if rounds else 0), _p(row), _p(slot), _p(ret), *tail)
+    return [ret[i, :len(r)].copy() for i, r in enumerate(rounds)]
+
+
+def pool_take(sub, s0_mask, sub_cap, base0, cur, n, cnt=None):
+    """One launch of len(n) blocks, lane 0 of block b calling pool_take(d, cur,
+    n[b]); a block with n[b] == 0 makes no call.  Returns (result per block as uint64, poolCnt [2][sub][16] after,
+    err); cnt: poolCnt before (default zeros)."""
+    n = _in(n, np.uint64)
+    cnt = np.zeros(2 * sub * 16, dtype=np.uint64) if cnt is None else _in(cnt, np.uint64, 2 * sub * 16).copy()
+    out = np.zeros(n.size, dtype=np.uint64)
+    err = np.zeros(1, dtype=np.int32)
+    _call("gsp_pool_take", C.c_int(sub), C.c_int(s0_mask), C.c_int64(sub_cap), C.c_int64(base0), C.c_int(cur),
+          C.c_int(n.size), _p(n), _p(out), _p(cnt), _p(err))
+    return out, cnt.reshape(2, sub, 16), int(err[0])

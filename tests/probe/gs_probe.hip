@@ -8,7 +8,9 @@
 // Every wrapper launches blocks of exactly 64 threads (one wave: select_kth
 // and select_kth_est use __syncthreads and are wave-uniform calls), one case
 // per block, all cases of a test in one launch.  Every loop is bounded by the
-// wrapper's inputs.
+// wrapper's inputs.  Two entry points launch kernels of the product itself,
+// in the engine's geometry: gsp_ptx_rebuild (the heartbeat's peertx rebuild,
+// through the engine's own ptx_rebuild_launch) and gsp_spam (k_retire).
 #include "../../go-libp2p-pubsub_amd/csrc/gs_device.h"
 #include "../../go-libp2p-pubsub_amd/csrc/gs_kernels.h"
 #include "../../go-libp2p-pubsub_amd/csrc/gs_kernels_ctl.h"
@@ -243,6 +245,22 @@ __global__ __launch_bounds__(64) void kp_ptx_count(Dev d, int n, const int32_t* 
   cntO[i] = ptxo_count(d, node[i], key[i]);
 }
 
+// ---- the spammers' nibble counters ---------------------------------------
+// one round: thread i does spam_incr(row[i], slot[i]); row < 0: no request.
+// The caller keeps (row, slot) distinct within a round, as the call sites do.
+__global__ __launch_bounds__(64) void kp_spam_round(Dev d, int n, const int32_t* row, const int32_t* slot, int32_t* ret) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n || row[i] < 0) return;
+  ret[i] = spam_incr(d, row[i], slot[i]);
+}
+
+// ---- pool_take -----------------------------------------------------------
+// lane 0 of block b asks for n[b] ids, as the kernels' one lane per wave does;
+// n[b] == 0: the block asks for nothing (no call site ever asks for 0 ids)
+__global__ __launch_bounds__(64) void kp_pool_take(Dev d, int cur, const unsigned long long* n, unsigned long long* out) {
+  if (threadIdx.x == 0 && n[blockIdx.x] != 0ull) out[blockIdx.x] = pool_take(d, cur, n[blockIdx.x]);
+}
+
 inline int blocks_of(int64_t n) { return (int)((n + 63) / 64); }
 
 }  // namespace
@@ -250,12 +268,13 @@ inline int blocks_of(int64_t n) { return (int)((n + 63) / 64); }
 extern "C" {
 
 // the constants the references need: out[0] = GS_SEL_WIN, [1] = GS_SEL_CAP,
-// [2] = E_PEERTX, [3] = number of gsp_lanes ops
+// [2] = E_PEERTX, [3] = number of gsp_lanes ops, [4] = E_POOL
 int gsp_consts(int32_t* out) {
   out[0] = GS_SEL_WIN;
   out[1] = GS_SEL_CAP;
   out[2] = E_PEERTX;
   out[3] = OP_COUNT;
+  out[4] = E_POOL;
   return 0;
 }
 
@@ -467,6 +486,162 @@ int gsp_peertx(int ptxBits, int ptxOBits, int GR, int nNodes, uint32_t* rows, ui
   B.back(ins, dins, nOps);
   B.back(cntG, dcg, nQ);
   B.back(cntO, dco, nQ);
+  return (int)B.err;
+}
+
+// hipDeviceAttributeMaxSharedMemoryPerBlock of the current device: what bounds
+// gs_set_peertx_capacity's home_bits (the rebuild's 4 << ptxBits bytes of LDS)
+int gsp_lds_limit(int32_t* out) {
+  int dev = 0, lim = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+  out[0] = lim;
+  return (int)e;
+}
+
+// The heartbeat's peertx rebuild, once: k_ptx_rebuild, k_ptxo_collect,
+// k_ptxo_reinsert, k_ptxo_fin through ptx_rebuild_launch, the engine's own
+// launch function, over nNodes owned nodes (n0 = 0, nOwnH = nNodes).  rows
+// [nNodes << ptxBits], ptxN [nNodes], ovf [1 << ptxOBits] and ocnt [3] are
+// in/out (the layout of gsp_peertx); hist is the mcache ring [R][nNodes][W]
+// and `last` the ring row of the window leaving the cache.  Refused before any
+// launch: a row that does not fit the device's LDS, an entry whose slot lies
+// outside hist's W words or whose node tag is not a node, and counters that
+// would let the staging index start above 0 (the stage holds 1 << ptxOBits).
+int gsp_ptx_rebuild(int ptxBits, int ptxOBits, int nNodes, uint32_t* rows, int32_t* ptxN, uint64_t* ovf, uint32_t* ocnt,
+                    int R, int W, int last, const uint64_t* hist) {
+  if (ptxBits < 2 || ptxBits > 16 || ptxOBits < 1 || ptxOBits > 20 || nNodes < 1 || nNodes > (1 << 20) || R < 1 || W < 1 ||
+      W > 256 || last < 0 || last >= R || ocnt[1] != 0u || ocnt[2] != 0u)
+    return (int)hipErrorInvalidValue;
+  int32_t lim = 0;
+  if (const int e = gsp_lds_limit(&lim)) return e;
+  if (ptx_rebuild_lds(ptxBits) > (size_t)lim) return (int)hipErrorInvalidValue;
+  const size_t nRow = (size_t)nNodes << ptxBits, nOvf = (size_t)1 << ptxOBits;
+  const uint32_t nSlots = (uint32_t)W * 64u;
+  for (size_t i = 0; i < nRow; ++i)
+    if (rows[i] != 0u && (rows[i] >> 14) >= nSlots) return (int)hipErrorInvalidValue;
+  for (size_t i = 0; i < nOvf; ++i) {
+    if (ovf[i] == 0ull) continue;
+    const uint64_t tag = ovf[i] >> 32;
+    if (tag < 1 || tag > (uint64_t)nNodes || ((uint32_t)ovf[i] >> 14) >= nSlots) return (int)hipErrorInvalidValue;
+  }
+  Bufs B;
+  Dev d;
+  std::memset(&d, 0, sizeof(d));
+  d.ptxBits = ptxBits;
+  d.ptxOBits = ptxOBits;
+  d.n0 = 0;
+  d.n1 = d.N = d.nOwnH = nNodes;
+  d.W = W;
+  d.R = R;
+  d.ptxT = B.dev(rows, nRow);
+  d.ptxN = B.dev(ptxN, nNodes);
+  d.ptxO = (unsigned long long*)B.dev(ovf, nOvf);
+  d.ptxOStage = B.dev<unsigned long long>(nullptr, nOvf);
+  d.ptxOCnt = B.dev(ocnt, 3);
+  d.hist = B.dev(hist, (size_t)R * nNodes * W);
+  if (B.ok()) ptx_rebuild_launch(d, nNodes, last, 0);
+  B.sync();
+  B.back(rows, d.ptxT, nRow);
+  B.back(ptxN, d.ptxN, nNodes);
+  B.back((unsigned long long*)ovf, d.ptxO, nOvf);
+  B.back(ocnt, d.ptxOCnt, 3);
+  return (int)B.err;
+}
+
+// nRounds rounds of perRound spam_incr(row, slot) calls (one launch per round;
+// row < 0: no request), then with doRetire one launch of k_retire alone, in
+// the engine's geometry, over the CSR rowptr [nNodes + 1] / spamRow [edges]
+// with pubmask[cur] = pubmask [S / 64] and the words[] list.  spamCnt
+// [nRows][S / 8] and pmask [nPm][S] are in/out.  spamRow or pmaskRow
+// [nNodes] == nullptr leaves that half of k_retire off, as in the engine.
+int gsp_spam(int S, int GR, int nRows, uint32_t* spamCnt, int nRounds, int perRound, const int32_t* row,
+             const int32_t* slot, int32_t* ret, int doRetire, int cur, int nNodes, const int64_t* rowptr,
+             const int32_t* spamRow, const uint64_t* pubmask, int nwords, const int32_t* words, const int32_t* pmaskRow,
+             int nPm, uint64_t* pmask) {
+  if (S < 64 || S % 64 != 0 || S > (1 << 14) || GR < 0 || GR > 13 || nRows < 1 || nRounds < 0 || perRound < 0)
+    return (int)hipErrorInvalidValue;
+  const size_t nOps = (size_t)nRounds * perRound;
+  for (size_t i = 0; i < nOps; ++i)
+    if (row[i] >= nRows || (row[i] >= 0 && (slot[i] < 0 || slot[i] >= S))) return (int)hipErrorInvalidValue;
+  int64_t nEdges = 0;
+  if (doRetire) {
+    if (cur < 0 || cur > 1 || nNodes < 1 || nwords < 1 || nPm < 0 || rowptr[0] != 0) return (int)hipErrorInvalidValue;
+    for (int v = 0; v < nNodes; ++v)
+      if (rowptr[v] > rowptr[v + 1]) return (int)hipErrorInvalidValue;
+    nEdges = rowptr[nNodes];
+    for (int64_t e = 0; spamRow != nullptr && e < nEdges; ++e)
+      if (spamRow[e] >= nRows) return (int)hipErrorInvalidValue;
+    for (int k = 0; k < nwords; ++k)
+      if (words[k] < 0 || words[k] >= S / 64) return (int)hipErrorInvalidValue;
+    for (int v = 0; pmaskRow != nullptr && v < nNodes; ++v)
+      if (pmaskRow[v] >= nPm) return (int)hipErrorInvalidValue;
+  }
+  Bufs B;
+  const size_t nCnt = (size_t)nRows * (S / 8), nMask = (size_t)nPm * S;
+  Dev d;
+  std::memset(&d, 0, sizeof(d));
+  d.S = S;
+  d.W = S / 64;
+  d.GR = GR;
+  d.spamCnt = B.dev(spamCnt, nCnt);
+  auto* drow = B.dev(row, nOps);
+  auto* dslot = B.dev(slot, nOps);
+  auto* dret = B.dev<int32_t>(nullptr, nOps);
+  for (int r = 0; r < nRounds && perRound > 0 && B.ok(); ++r) {
+    const size_t o = (size_t)r * perRound;
+    hipLaunchKernelGGL(kp_spam_round, dim3(blocks_of(perRound)), dim3(64), 0, 0, d, perRound, drow + o, dslot + o, dret + o);
+    B.sync();  // the barrier between rounds
+  }
+  if (doRetire) {
+    d.n0 = 0;
+    d.n1 = d.N = nNodes;
+    d.rowptr = B.dev(rowptr, (size_t)nNodes + 1);
+    if (spamRow != nullptr) d.spamRow = B.dev(spamRow, (size_t)nEdges);
+    d.pubmask[cur] = B.dev(pubmask, (size_t)S / 64);
+    if (pmaskRow != nullptr) {
+      d.pmaskRow = B.dev(pmaskRow, nNodes);
+      d.pmask = B.dev(pmask, nMask);
+    }
+    auto* dwords = B.dev(words, nwords);
+    const int64_t nThreads = (int64_t)nNodes * nwords;
+    if (B.ok()) hipLaunchKernelGGL(k_retire, dim3((unsigned)((nThreads + 255) / 256)), dim3(256), 0, 0, d, cur, dwords, nwords);
+    B.sync();
+    if (pmaskRow != nullptr) B.back(pmask, d.pmask, nMask);
+  }
+  B.back(spamCnt, d.spamCnt, nCnt);
+  B.back(ret, dret, nOps);
+  return (int)B.err;
+}
+
+// One launch of nBlocks blocks; lane 0 of block b calls pool_take(d, cur,
+// n[b]) and out[b] is its result (n[b] == 0: no call, out[b] = 0).  poolCnt
+// [2][poolSub * 16] and err [1] are in/out.
+int gsp_pool_take(int poolSub, int poolS0Mask, int64_t poolSubCap, int64_t poolBase0, int cur, int nBlocks,
+                  const uint64_t* n, uint64_t* out, uint64_t* poolCnt, int32_t* err) {
+  if (poolSub < 1 || poolSub > 64 || (poolSub & (poolSub - 1)) != 0 || poolS0Mask < 0 || poolSubCap < 0 ||
+      poolSubCap > ((int64_t)1 << 40) || poolBase0 < 0 || cur < 0 || cur > 1 || nBlocks < 1 || nBlocks > (1 << 20))
+    return (int)hipErrorInvalidValue;
+  for (int b = 0; b < nBlocks; ++b)
+    if (n[b] > (1ull << 31)) return (int)hipErrorInvalidValue;
+  Bufs B;
+  const size_t nCnt = (size_t)2 * poolSub * 16;
+  Dev d;
+  std::memset(&d, 0, sizeof(d));
+  d.poolSub = poolSub;
+  d.poolS0Mask = poolS0Mask;
+  d.poolSubCap = poolSubCap;
+  d.poolBase0 = poolBase0;
+  d.poolCap = poolSubCap * poolSub;
+  d.poolCnt = (unsigned long long*)B.dev(poolCnt, nCnt);
+  d.err = B.dev(err, 1);
+  auto* dn = (const unsigned long long*)B.dev(n, nBlocks);
+  auto* dout = B.dev<unsigned long long>(nullptr, nBlocks);
+  if (B.ok()) hipLaunchKernelGGL(kp_pool_take, dim3(nBlocks), dim3(64), 0, 0, d, cur, dn, dout);
+  B.sync();
+  B.back(out, (const uint64_t*)dout, nBlocks);
+  B.back(poolCnt, (const uint64_t*)d.poolCnt, nCnt);
+  B.back(err, d.err, 1);
   return (int)B.err;
 }
 

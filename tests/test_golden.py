@@ -74,3 +74,38 @@ def test_gpu_peertx_overflow_full_is_capacity_error():
     with pytest.raises(GossipEngineError) as ei:
         scenarios.run(PRODUCT_LIB, "c3shape", extra=(WithPeertxCapacity(2, 8),))
     assert ei.value.code == _abi.GS_ECAPACITY and "overflow table" in str(ei.value)
+
+
+def _largest_home_bits():
+    """The largest gs_set_peertx_capacity home_bits whose row (4 << home_bits
+    bytes, staged in LDS by the heartbeat's rebuild) fits the device's LDS per
+    workgroup; 16 is the API's own limit."""
+    import probe
+    lim = probe.lds_limit()
+    fits = [b for b in range(2, 17) if (4 << b) <= lim]
+    assert fits, lim
+    return max(fits), lim
+
+
+@pytest.mark.gpu
+def test_gpu_peertx_largest_home_bits_reproduces_golden():
+    """The heartbeat's rebuild with the largest row the device's LDS holds (15
+    where a workgroup has 160 KiB: 128 KiB of dynamic LDS per launch)."""
+    from pubsub_amd import PRODUCT_LIB, WithPeertxCapacity
+    bits, lim = _largest_home_bits()
+    print(f"LDS per workgroup {lim} bytes: largest home_bits {bits}")
+    assert digest(scenarios.run(PRODUCT_LIB, "c3shape", extra=(WithPeertxCapacity(bits, 16),))) == GOLDEN["c3shape"]
+
+
+@pytest.mark.gpu
+def test_gpu_peertx_home_bits_above_lds_is_capacity_error():
+    """One above that is refused by name when the tables are sized, before any
+    kernel runs, not by a failed launch at the first heartbeat."""
+    from pubsub_amd import PRODUCT_LIB, GossipEngineError, WithPeertxCapacity, _abi
+    bits, lim = _largest_home_bits()
+    assert bits < 16  # (gs_set_peertx_capacity itself stops at 16)
+    with pytest.raises(GossipEngineError) as ei:
+        scenarios.run(PRODUCT_LIB, "c3shape", extra=(WithPeertxCapacity(bits + 1, 16),))
+    msg = str(ei.value)
+    assert ei.value.code == _abi.GS_ECAPACITY
+    assert f"home_bits {bits + 1}" in msg and str(4 << (bits + 1)) in msg and str(lim) in msg
