@@ -142,6 +142,8 @@ struct Dev {
   const AcctT* acc;            // [T]
   int32_t acctIdF;             // one message id inside an IHAVE / IWANT
   int32_t acctPiF;             // one PX PeerInfo inside a ControlPrune
+  // bandwidth statistics (gs_set_bandwidth_stats); nullptr: off
+  unsigned long long* bwX;     // [E][2] of rpcB[e]: the eager bytes (k_acct_payload), the pulled bytes (IWANT replies)
   // EventTracer of the hosts with traced[u] != 0 (gs_set_trace); nullptr = off
   const uint8_t* traced;
   gs_trace_event* trace;

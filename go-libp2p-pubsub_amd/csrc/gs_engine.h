@@ -28,6 +28,7 @@
 #include "../../include/gs_inspect.h"
 #include "../../include/gs_mesh_health.h"
 #include "../../include/gs_mesh_reach.h"
+#include "../../include/gs_bandwidth.h"
 #include "../../include/gs_window.h"
 #include "gs_window_layout.h"
 #include "gs_host.h"
@@ -37,6 +38,7 @@
 #include "gs_kernels_insp.h"
 #include "gs_kernels_mesh.h"
 #include "gs_kernels_reach.h"
+#include "gs_kernels_bw.h"
 #include "gs_exchange.h"
 
 #define HIPCHECK(expr)                                                        \
@@ -454,6 +456,19 @@ struct gs_engine {
   unsigned long long *dReachRows = nullptr, *dReachWords = nullptr;
   unsigned reachGrid = 0;
   int64_t reachPasses = 0, reachLevels = 0, reachBytes = 0;  // since the start or the last gs_set_profiling
+  // bandwidth statistics (gs_bandwidth.h): the per-node tables (uint64 [N][8]:
+  // the cumulative sums at the previous tick, this tick's deltas), a ring of
+  // bwCap rows (bw_row_len) and the sampled nodes' values (k_bw_gather's layout)
+  bool bwOn = false;
+  int64_t bwPeriod = 0, bwTaken = 0;
+  int bwCap = 0;
+  std::vector<int64_t> bwBounds;
+  std::vector<int32_t> bwNodes;      // the sampled nodes, ascending
+  long long* dBwBounds = nullptr;
+  int32_t* dBwNodes = nullptr;
+  unsigned long long *dBwPrev = nullptr, *dBwDelta = nullptr, *dBwRows = nullptr, *dBwBytes = nullptr, *dBwRpcs = nullptr;
+  unsigned bwGrid = 0;
+  int bwRowLen() const { return bw_row_len((int)bwBounds.size()); }
   // kernel timing: (kernel id, start event, end event) pending until a sync
   bool profiling = false;
   std::vector<hipEvent_t> evPool;
@@ -461,12 +476,14 @@ struct gs_engine {
   std::vector<int> pendKid;
   // (past the public kernel ids: the latency kernels, gs_read_latency_kernel_stats, and the
   // inspection's three passes, gs_read_inspect_kernel_stats; mesh health's four,
-  // gs_read_mesh_health_kernel_stats; mesh reach's four, gs_read_mesh_reach_kernel_stats)
+  // gs_read_mesh_health_kernel_stats; mesh reach's four, gs_read_mesh_reach_kernel_stats; the
+  // bandwidth statistics' three, gs_read_bandwidth_kernel_stats)
   static constexpr int kLatCount = GS_NUM_KERNELS, kLatFold = GS_NUM_KERNELS + 1;
   static constexpr int kInspScore = GS_NUM_KERNELS + 2, kInspReduce = GS_NUM_KERNELS + 3;
   static constexpr int kInspGather = GS_NUM_KERNELS + 4, kMeshInit = GS_NUM_KERNELS + 5;
   static constexpr int kReachMembers = kMeshInit + 4;  // (kMeshInit + GS_MESH_K_*)
-  static constexpr int kTimed = kReachMembers + 4;     // (kReachMembers + GS_REACH_K_*)
+  static constexpr int kBwTick = kReachMembers + 4;    // (kReachMembers + GS_REACH_K_*)
+  static constexpr int kTimed = kBwTick + GS_BW_NUM_STATS;  // (kBwTick + GS_BW_K_*)
   double kMs[kTimed] = {0};
   int64_t kLaunches[kTimed] = {0};
   hipEvent_t nextEvent() {
@@ -569,6 +586,10 @@ struct gs_engine {
     dReachMembers = dReachFlag = nullptr;
     dReachRows = dReachWords = nullptr;
     reachTaken = 0;
+    dBwBounds = nullptr;
+    dBwNodes = nullptr;
+    dBwPrev = dBwDelta = dBwRows = dBwBytes = dBwRpcs = nullptr;
+    bwTaken = 0;
     started = churnOn = allocFailed = false;
     uploaded = 0;
     aliveH.clear();
@@ -642,6 +663,7 @@ struct gs_engine {
   int allocInspect(), inspectTick();
   int allocMeshHealth(), meshTick();
   int allocMeshReach(), reachTick();
+  int allocBandwidth(), bandwidthTick();
   void refreshOrFold(const Hop& hp), heartbeat(const Hop& hp);
   template <bool ADV>
   PhaseADev<ADV> phaseADev() const {

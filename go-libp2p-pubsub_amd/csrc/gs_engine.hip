@@ -182,6 +182,7 @@ int gs_engine::buildDevice(const Plan& pl) {
   GS_TRY(allocFail("state", "; reduce num_nodes or slots_per_topic"));
   GS_TRY(initConnections(pl));
   GS_TRY(allocAcct(pl));
+  GS_TRY(allocBandwidth());
   started = true;
   return uploadMessages();
 }
@@ -839,6 +840,61 @@ int gs_engine::meshTick() {
   return GS_OK;
 }
 
+// Bandwidth statistics (gs_bandwidth.h) at their exact sizes: the split
+// counters of every edge, the two per-node tables, the ring of rows and of the
+// sampled nodes' values; k_bw_tick's grid.  After allocAcct: the counters
+// start at zero, as the hello packets are overhead.
+int gs_engine::allocBandwidth() {
+  if (!bwOn) return GS_OK;
+  const size_t nS = bwNodes.size(), cap = (size_t)bwCap, nb = bwBounds.size();
+  const bool before = allocFailed;
+  allocFailed = false;
+  d.bwX = ealloc<unsigned long long>(0, 2);
+  dBwPrev = dalloc<unsigned long long>((size_t)N * GS_BW_NODE_WORDS);
+  dBwDelta = dalloc<unsigned long long>((size_t)N * GS_BW_NODE_WORDS);
+  dBwRows = dalloc<unsigned long long>(cap * (size_t)bwRowLen());
+  dBwBounds = dalloc<long long>(std::max<size_t>(nb, 1));
+  if (nS) {
+    dBwNodes = dalloc<int32_t>(nS);
+    dBwBytes = dalloc<unsigned long long>(cap * nS * GS_BW_NODE_WORDS);
+    dBwRpcs = dalloc<unsigned long long>(cap * nS * GS_BW_DIRS);
+  }
+  if (allocFailed) return allocFail("bandwidth statistics", "; reduce ticks or the sampled nodes");
+  allocFailed = before;
+  GS_TRY(put(dBwBounds, reinterpret_cast<const long long*>(bwBounds.data()), nb));
+  GS_TRY(putNow(dBwNodes, bwNodes.data(), nS));
+  int cus = 0;
+  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
+  bwGrid = GS_BW_WGS_PER_CU * (unsigned)std::max(cus, 1);
+  return GS_OK;
+}
+
+// A tick at the end of a hop (`hop` already counts it): the row and the
+// sampled nodes into the tick's ring slot.  Nothing is read back: the host
+// knows a tick's hop.
+int gs_engine::bandwidthTick() {
+  const int slot = (int)(bwTaken % bwCap);
+  const int64_t nS = (int64_t)bwNodes.size();
+  unsigned long long* row = dBwRows + (size_t)slot * bwRowLen();
+  HIPCHECK(hipMemsetAsync(row, 0, (size_t)bwRowLen() * 8, stream));
+  HIPCHECK(hipMemsetAsync(row + GS_BW_ROW_ARG, 0xFF, (size_t)GS_BW_DIRS * GS_BW_CLASSES * 8, stream));  // -1: no node
+  if (nOwn()) {
+    const unsigned grid = std::min(bwGrid, nblk(nOwn(), GS_BW_BLOCK / 64));
+    TIMED(this, kBwTick + GS_BW_K_TICK, (k_bw_tick<<<grid, GS_BW_BLOCK, 0, stream>>>(
+                                            d, dBwBounds, (int)bwBounds.size(), dBwPrev, dBwDelta, row)));
+    TIMED(this, kBwTick + GS_BW_K_ARGMAX,
+          (k_bw_argmax<<<nblk((int64_t)nOwn() * GS_BW_NODE_WORDS, 256), 256, 0, stream>>>(d, dBwDelta, row)));
+  }
+  if (nS)
+    TIMED(this, kBwTick + GS_BW_K_GATHER,
+          (k_bw_gather<<<nblk(nS * GS_BW_NODE_WORDS, 256), 256, 0, stream>>>(
+              dBwNodes, nS, dBwDelta, dBwBytes + (size_t)slot * nS * GS_BW_NODE_WORDS,
+              dBwRpcs + (size_t)slot * nS * GS_BW_DIRS)));
+  HIPCHECK(hipGetLastError());
+  bwTaken++;
+  return GS_OK;
+}
+
 // Mesh reach (gs_mesh_reach.h) at its exact sizes: the two bit tables, the ring
 // of rows, the sources, the include mask, the members per topic, a batch's
 // flags, the byte counters and, when asked for, the depth table; the grid of
@@ -1312,6 +1368,7 @@ int gs_engine::stepOne() {
   if (inspOn && hop % inspPeriod == 0) GS_TRY(inspectTick());
   if (meshOn && hop % meshPeriod == 0) GS_TRY(meshTick());
   if (reachOn && hop % reachPeriod == 0) GS_TRY(reachTick());
+  if (bwOn && hop % bwPeriod == 0) GS_TRY(bandwidthTick());
   return GS_OK;
 }
 
@@ -2355,6 +2412,7 @@ int gs_set_partition(gs_engine* g, int32_t rank, int32_t world, const gs_transpo
   if (g->started) { gs_set_error("the partition must be set before the first step"); return GS_ESTATE; }
   if (world < 1 || world > 255 || rank < 0 || rank >= world) { gs_set_error("bad rank / world"); return GS_EINVAL; }
   if (world > 1 && g->meshOn) { gs_set_error("mesh health: not on a partitioned engine"); return GS_EUNSUPPORTED; }
+  if (world > 1 && g->bwOn) { gs_set_error("bandwidth statistics: not on a partitioned engine"); return GS_EUNSUPPORTED; }
   if (world > 1 && g->reachOn) { gs_set_error("mesh reach: not on a partitioned engine"); return GS_EUNSUPPORTED; }
   if (world > 1 && (!tr || !tr->allgather_i64 || !tr->allgather || !tr->alltoallv)) {
     gs_set_error("a partitioned engine needs a transport with allgather_i64, allgather and alltoallv");
@@ -2974,6 +3032,118 @@ int gs_read_mesh_health_kernel_stats(gs_engine* g, double* total_ms, int64_t* la
   total_ms[GS_MESH_ST_ITERS] = total_ms[GS_MESH_ST_BYTES] = 0.0;
   launches[GS_MESH_ST_ITERS] = g->meshIters;
   launches[GS_MESH_ST_BYTES] = g->meshBytes;
+  return GS_OK;
+}
+
+// ---- bandwidth statistics (include/gs_bandwidth.h)
+int gs_set_bandwidth_stats(gs_engine* g, const gs_bandwidth_config* c) {
+  if (g->started) { gs_set_error("the bandwidth statistics must be set before the first step"); return GS_ESTATE; }
+  if (g->bwOn) { gs_set_error("duplicate bandwidth statistics"); return GS_ESTATE; }
+  if (!g->acctOn) { gs_set_error("bandwidth statistics: RPC accounting is off"); return GS_ESTATE; }
+  if (g->world > 1) { gs_set_error("bandwidth statistics: not on a partitioned engine"); return GS_EUNSUPPORTED; }
+  if (!c || c->period_hops <= 0) { gs_set_error("bandwidth statistics: period_hops must be positive"); return GS_EINVAL; }
+  if (c->ticks < 1) { gs_set_error("bandwidth statistics: ticks must be at least 1"); return GS_EINVAL; }
+  if (c->num_bounds < 0 || c->num_bounds > GS_BW_MAX_BOUNDS || (c->num_bounds > 0 && !c->bounds)) {
+    gs_set_error("bandwidth statistics: num_bounds must be 0.." + std::to_string(GS_BW_MAX_BOUNDS));
+    return GS_EINVAL;
+  }
+  for (int i = 0; i < c->num_bounds; ++i)
+    if (c->bounds[i] <= 0 || (i > 0 && !(c->bounds[i - 1] < c->bounds[i]))) {
+      gs_set_error("bandwidth statistics: bounds must be positive and strictly ascending");
+      return GS_EINVAL;
+    }
+  g->bwPeriod = c->period_hops;
+  g->bwCap = c->ticks;
+  g->bwBounds.assign(c->bounds, c->bounds + c->num_bounds);
+  g->bwNodes.clear();
+  if (c->node_mask)
+    for (int u = 0; u < g->N; ++u)
+      if (c->node_mask[u]) g->bwNodes.push_back(u);
+  g->bwOn = true;
+  return GS_OK;
+}
+
+static int bandwidth_on(const gs_engine* g) {
+  if (!g->bwOn) { gs_set_error("the bandwidth statistics are off (gs_set_bandwidth_stats)"); return GS_ESTATE; }
+  return GS_OK;
+}
+
+// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
+static int bandwidth_tick_ok(const gs_engine* g, int64_t tick) {
+  GS_TRY(bandwidth_on(g));
+  if (tick < 0 || tick >= g->bwTaken) {
+    gs_set_error("bandwidth statistics: tick " + std::to_string(tick) + " not taken yet (" +
+                 std::to_string(g->bwTaken) + " so far)");
+    return GS_EINVAL;
+  }
+  if (tick < g->bwTaken - g->bwCap) {
+    gs_set_error("bandwidth statistics: tick " + std::to_string(tick) + " already overwritten (ring of " +
+                 std::to_string(g->bwCap) + ")");
+    return GS_ESTATE;
+  }
+  return GS_OK;
+}
+
+int64_t gs_bandwidth_ticks(const gs_engine* g) {
+  GS_TRY(bandwidth_on(g));
+  return g->bwTaken;
+}
+
+int gs_bandwidth_num_nodes(const gs_engine* g, int64_t* n) {
+  GS_TRY(bandwidth_on(g));
+  *n = (int64_t)g->bwNodes.size();
+  return GS_OK;
+}
+
+int gs_bandwidth_nodes(gs_engine* g, int32_t* nodes, int64_t cap) {
+  int64_t n = 0;
+  GS_TRY(gs_bandwidth_num_nodes(g, &n));
+  if (cap < n || (n > 0 && !nodes)) { gs_set_error("bandwidth statistics: node buffer too small"); return GS_EINVAL; }
+  std::copy(g->bwNodes.begin(), g->bwNodes.end(), nodes);
+  return GS_OK;
+}
+
+int gs_read_bandwidth_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* total, int64_t* total_rpcs,
+                          int64_t* hist, int64_t* max, int64_t* argmax) {
+  GS_TRY(bandwidth_tick_ok(g, tick));
+  if (hop) *hop = (tick + 1) * g->bwPeriod;
+  const unsigned long long* row = g->dBwRows + (size_t)(tick % g->bwCap) * g->bwRowLen();
+  const size_t nw = (size_t)GS_BW_DIRS * GS_BW_CLASSES;
+  const auto get = [&](int64_t* dst, size_t at, size_t n) {
+    return dst ? hipMemcpyAsync(dst, row + at, n * 8, hipMemcpyDeviceToHost, g->stream) : hipSuccess;
+  };
+  HIPCHECK(get(total, 0, GS_BW_CLASSES));
+  HIPCHECK(get(total_rpcs, GS_BW_CLASSES, 1));
+  HIPCHECK(get(max, GS_BW_ROW_MAX, nw));
+  HIPCHECK(get(argmax, GS_BW_ROW_ARG, nw));
+  HIPCHECK(get(hist, GS_BW_ROW_HIST, nw * (g->bwBounds.size() + 1)));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_bandwidth_nodes(gs_engine* g, int64_t tick, int64_t* bytes, int64_t* rpcs) {
+  GS_TRY(bandwidth_tick_ok(g, tick));
+  const size_t nS = g->bwNodes.size(), slot = (size_t)(tick % g->bwCap);
+  if (nS && bytes)
+    HIPCHECK(hipMemcpyAsync(bytes, g->dBwBytes + slot * nS * GS_BW_NODE_WORDS, nS * GS_BW_NODE_WORDS * 8,
+                            hipMemcpyDeviceToHost, g->stream));
+  if (nS && rpcs)
+    HIPCHECK(hipMemcpyAsync(rpcs, g->dBwRpcs + slot * nS * GS_BW_DIRS, nS * GS_BW_DIRS * 8, hipMemcpyDeviceToHost,
+                            g->stream));
+  HIPCHECK(hipStreamSynchronize(g->stream));
+  return GS_OK;
+}
+
+int gs_read_bandwidth_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
+  GS_TRY(bandwidth_on(g));
+  if (g->started) {
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    g->resolveTimings();
+  }
+  for (int i = 0; i < GS_BW_NUM_STATS; ++i) {
+    total_ms[i] = g->kMs[gs_engine::kBwTick + i];
+    launches[i] = g->kLaunches[gs_engine::kBwTick + i];
+  }
   return GS_OK;
 }
 

@@ -2589,7 +2589,10 @@ __global__ __launch_bounds__(64) void k_acct_payload(Dev d, int p) {
       }
     }
   }
-  if (valid && n) acct_send(d, e, (int64_t)b, (int)n);
+  if (valid && n) {
+    acct_send(d, e, (int64_t)b, (int)n);
+    if (d.bwX != nullptr) d.bwX[2 * e] += b;  // the eager class (gs_bandwidth.h)
+  }
 }
 
 // RPC accounting: (edge, bytes) pairs of the host-side RPCs of a hop

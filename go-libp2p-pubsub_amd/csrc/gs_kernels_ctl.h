@@ -1327,6 +1327,8 @@ __device__ __forceinline__ void phase_b_node(const Dev& d, const int v, int64_t 
             b += gs_pb_field(body);
           }
           acct_send(d, e, b, nReplies);
+          // the pulled class (gs_bandwidth.h): the served messages, without their control
+          if (d.bwX != nullptr && (srvB | srvBS)) d.bwX[2 * e + 1] += (unsigned long long)srvB + srvBS;
         }
         if (rpc_traced(d, v, u)) {
           // HandleRPC's replies (gossipsub.go:602-607), each named by the RPC it

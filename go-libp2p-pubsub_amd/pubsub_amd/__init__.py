@@ -19,4 +19,4 @@ from .engine import (PRODUCT_LIB, Engine, GossipEngineError, NewFloodSub, NewGos
                      WithBehaviour, WithPeerGater, WithRPCAccounting, WithValidation, WithPeerExchange, WithDormant,
                      WithRouters, WithProtocols, WithIPWhitelist, WithLatencyStats, WithTopicWindows, latency_quantiles,
                      WithMeshHealth, WithMeshReach, WithPeerScoreInspect, PeerScoreSnapshot, TopicScoreSnapshot, default_inspect_bounds,
-                     load)
+                     WithBandwidthStats, bandwidth_quantiles, default_bandwidth_bounds, load)

@@ -300,6 +300,29 @@ MESH_REACH_FUNCTIONS = [
 REACH_KERNEL_NAMES = ["reach_members", "reach_init", "reach_level", "reach_finish"]
 REACH_STAT_NAMES = REACH_KERNEL_NAMES + ["passes", "levels", "bytes"]
 
+# include/gs_bandwidth.h (product library only; bound by Engine with WithBandwidthStats)
+GS_BW_MAX_BOUNDS = 63
+BW_DIRS = ["egress", "ingress"]
+BW_CLASSES = ["all", "eager", "pulled", "overhead"]
+
+
+class BandwidthConfigC(C.Structure):
+    _fields_ = [("period_hops", i64), ("ticks", i32), ("num_bounds", i32), ("bounds", C.POINTER(i64)),
+                ("node_mask", C.POINTER(u8))]
+
+
+BANDWIDTH_FUNCTIONS = [
+    ("gs_set_bandwidth_stats", C.c_int, [P, C.POINTER(BandwidthConfigC)]),
+    ("gs_bandwidth_ticks", i64, [P]),
+    ("gs_bandwidth_num_nodes", C.c_int, [P, C.POINTER(i64)]),
+    ("gs_bandwidth_nodes", C.c_int, [P, C.POINTER(i32), i64]),
+    ("gs_read_bandwidth_row", C.c_int,
+     [P, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    ("gs_read_bandwidth_nodes", C.c_int, [P, i64, C.POINTER(i64), C.POINTER(i64)]),
+    ("gs_read_bandwidth_kernel_stats", C.c_int, [P, C.POINTER(f64), C.POINTER(i64)]),
+]
+BANDWIDTH_KERNEL_NAMES = ["bw_tick", "bw_argmax", "bw_gather"]
+
 KERNEL_NAMES = ["score", "refresh", "join", "fanout", "fwd", "phase_a", "publish", "phase_b",
                 "hb_pre", "heartbeat", "push"]
 

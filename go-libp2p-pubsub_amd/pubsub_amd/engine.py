@@ -330,6 +330,60 @@ def WithMeshReach(period, sources, *, nodes=None, ticks=64, depths=False):
                                depths=bool(depths)))
 
 
+def default_bandwidth_bounds():
+    """WithBandwidthStats' default bin bounds in bytes: 1 (bin 0 holds the
+    silent nodes), then the powers of 4 from 1 KiB to 16 GiB."""
+    return [1] + [1 << s for s in range(10, 35, 2)]
+
+
+def _checked_bandwidth_bounds(bounds):
+    b = np.asarray(bounds)
+    if b.ndim != 1 or (len(b) and b.dtype.kind not in "iu"):
+        raise ValueError("WithBandwidthStats: bounds must be a list of byte counts (integers)")
+    if len(b) > _abi.GS_BW_MAX_BOUNDS:
+        raise ValueError(f"WithBandwidthStats: at most {_abi.GS_BW_MAX_BOUNDS} bounds, got {len(b)}")
+    if len(b) and int(b.max()) >= 1 << 63:
+        raise ValueError("WithBandwidthStats: bounds must fit 63 bits")
+    b = np.ascontiguousarray(b, dtype=np.int64)
+    if not (b > 0).all() or not (np.diff(b) > 0).all():
+        raise ValueError("WithBandwidthStats: bounds must be positive and strictly ascending")
+    return b
+
+
+def WithBandwidthStats(period, *, bounds=None, nodes=None, ticks=64):
+    """Bandwidth statistics (include/gs_bandwidth.h, product library only; needs
+    WithRPCAccounting, in any order): every `period` (ns, a positive multiple
+    of the hop) the engine reduces, inside step() and without a synchronise,
+    the bytes every host sent (egress) and was sent (ingress) in the period,
+    split into eager push, payload pulled through IWANT and overhead: their
+    totals, histograms over `bounds` (byte counts; default:
+    default_bandwidth_bounds()), the maxima and the hosts that attain them, and
+    the exact values of the hosts in `nodes` (indices or a bool mask), into a
+    ring of `ticks` ticks.  Read with Engine.bandwidth_row(),
+    bandwidth_sampled(); see bandwidth_quantiles().  Not on a partitioned
+    engine."""
+    if int(ticks) < 1:
+        raise ValueError("WithBandwidthStats: ticks must be at least 1")
+    bounds = _checked_bandwidth_bounds(default_bandwidth_bounds() if bounds is None else bounds)
+    return ("bandwidth", dict(period=int(period), bounds=bounds, nodes=nodes, ticks=int(ticks)))
+
+
+def bandwidth_quantiles(hist_row, bounds, qs):
+    """Per row of `hist_row` (hosts by their bytes over `bounds`, [..., len(bounds)
+    + 1]) and per q in `qs`, the upper edge of the first bin whose cumulative
+    count reaches q x the row's total: the smallest bound that the quantile lies
+    below (bounds[0] = 1: a silent host).  -1 for an empty row, and when the
+    quantile lies in the last, open bin.  q is taken as the decimal it is
+    written as, as latency_quantiles does.  Returns int64 [..., len(qs)]."""
+    b = np.asarray(bounds, dtype=np.int64)
+    hist_row = np.asarray(hist_row)
+    if hist_row.shape[-1] != len(b) + 1:
+        raise ValueError(f"bandwidth_quantiles: a row needs len(bounds) + 1 = {len(b) + 1} bins")
+    edge = np.concatenate([b, [-1]]).astype(np.int64)
+    bins = latency_quantiles(hist_row, qs)
+    return np.where(bins < 0, -1, edge[np.maximum(bins, 0)])
+
+
 def WithPartition(rank, world, transport):
     """Simulate only this rank's node range; exchange RPCs with the other
     ranks through `transport` (a pubsub_amd.transport.TorchTransport) once per
@@ -369,6 +423,16 @@ class Engine:
                 raise ValueError(f"WithMeshReach: nodes needs one entry per host ({num_nodes}), got {len(mr['nodes'])}")
             if mr["sources"].min() < 0 or mr["sources"].max() >= num_nodes:
                 raise ValueError(f"WithMeshReach: a source is outside 0 .. {num_nodes - 1}")
+        bw = opts.get("bandwidth")
+        if bw is not None:
+            bw = dict(bw, period_hops=_inspect_period_hops(bw["period"], cfg.hop_ns, "WithBandwidthStats"))
+            if bw["nodes"] is not None:
+                nodes = np.asarray(bw["nodes"])
+                if nodes.dtype == bool and len(nodes) != num_nodes:
+                    raise ValueError(f"WithBandwidthStats: a node mask needs one entry per host ({num_nodes}), "
+                                     f"got {len(nodes)}")
+                if nodes.dtype != bool and len(nodes) and (nodes.min() < 0 or nodes.max() >= num_nodes):
+                    raise ValueError(f"WithBandwidthStats: a node is outside 0 .. {num_nodes - 1}")
         flags = 0
         if score is not None:
             flags |= _abi.GS_FLAG_SCORING
@@ -520,6 +584,26 @@ class Engine:
             _check(self.lib, self.lib.gs_set_rpc_accounting(h, _ptr(ms, C.c_int32), idl, _ptr(tl, C.c_int32)))
             _check(self.lib, self.lib.gs_set_rpc_px_sizes(h, pid, rec))
         self.rpc_acct = acct is not None
+        # include/gs_bandwidth.h: exported by the product library only; after the accounting it needs
+        self._has_bandwidth = all(hasattr(self.lib, name) for name, _, _ in _abi.BANDWIDTH_FUNCTIONS)
+        if self._has_bandwidth:
+            for name, res, args in _abi.BANDWIDTH_FUNCTIONS:
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = res, args
+        self._bw_bounds = None
+        if bw is not None:
+            if not self._has_bandwidth:
+                self.close()
+            lib = self._bandwidth_lib()
+            mask = None
+            if bw["nodes"] is not None:
+                mask = np.zeros(num_nodes, dtype=np.uint8)
+                nodes = np.asarray(bw["nodes"])
+                mask[np.nonzero(nodes)[0] if nodes.dtype == bool else nodes.astype(np.int64)] = 1
+            bc = _abi.BandwidthConfigC(bw["period_hops"], bw["ticks"], len(bw["bounds"]), _ptr(bw["bounds"], C.c_int64),
+                                       _ptr(mask, C.c_uint8))
+            _check(lib, lib.gs_set_bandwidth_stats(h, C.byref(bc)))
+            self._bw_bounds = bw["bounds"]
         self.router = router
         self.hop_ns = cfg.hop_ns
         self.rank, self.world, self.transport = opts.get("partition", (0, 1, None))
@@ -934,6 +1018,64 @@ class Engine:
         _check(lib, lib.gs_read_mesh_health_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
         out = {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.MESH_KERNEL_NAMES)}
         return dict(out, iterations=int(cnt[4]), bytes=int(cnt[5]))
+
+    # ---------------------------------------------------------------- bandwidth statistics
+    def _bandwidth_lib(self):
+        if not self._has_bandwidth:
+            raise ValueError("bandwidth statistics (WithBandwidthStats): product library only")
+        return self.lib
+
+    def bandwidth_ticks(self):
+        """Ticks taken so far (gs_bandwidth_ticks)."""
+        lib = self._bandwidth_lib()
+        n = lib.gs_bandwidth_ticks(self.h)
+        if n < 0:
+            _check(lib, int(n))
+        return int(n)
+
+    def bandwidth_nodes(self):
+        """The sampled nodes, ascending (gs_bandwidth_nodes), int32 [nS]."""
+        lib = self._bandwidth_lib()
+        n = C.c_int64()
+        _check(lib, lib.gs_bandwidth_num_nodes(self.h, C.byref(n)))
+        nodes = np.zeros(n.value, dtype=np.int32)
+        _check(lib, lib.gs_bandwidth_nodes(self.h, _ptr(nodes, C.c_int32), n.value))
+        return nodes
+
+    def bandwidth_row(self, k):
+        """Tick k: dict(hop; total int64 [4] bytes per class (all, eager, pulled,
+        overhead); total_rpcs; hist int64 [2, 4, len(bounds) + 1] hosts by their
+        bytes (egress / ingress, class); max and argmax int64 [2, 4], argmax -1
+        where max is 0) (gs_read_bandwidth_row)."""
+        lib = self._bandwidth_lib()
+        nb = len(self._bw_bounds) if self._bw_bounds is not None else 0
+        hop, rpcs = C.c_int64(), C.c_int64()
+        total = np.zeros(4, dtype=np.int64)
+        hist = np.zeros((2, 4, nb + 1), dtype=np.int64)
+        mx, arg = np.zeros((2, 4), dtype=np.int64), np.zeros((2, 4), dtype=np.int64)
+        _check(lib, lib.gs_read_bandwidth_row(self.h, int(k), C.byref(hop), _ptr(total, C.c_int64), C.byref(rpcs),
+                                              _ptr(hist, C.c_int64), _ptr(mx, C.c_int64), _ptr(arg, C.c_int64)))
+        return dict(hop=hop.value, total=total, total_rpcs=rpcs.value, hist=hist, max=mx, argmax=arg)
+
+    def bandwidth_sampled(self, k):
+        """Tick k: (bytes int64 [nS, 2, 4], rpcs int64 [nS, 2]) of the sampled
+        nodes, in bandwidth_nodes() order (gs_read_bandwidth_nodes)."""
+        lib = self._bandwidth_lib()
+        n = C.c_int64()
+        _check(lib, lib.gs_bandwidth_num_nodes(self.h, C.byref(n)))
+        b = np.zeros((n.value, 2, 4), dtype=np.int64)
+        r = np.zeros((n.value, 2), dtype=np.int64)
+        _check(lib, lib.gs_read_bandwidth_nodes(self.h, int(k), _ptr(b, C.c_int64), _ptr(r, C.c_int64)))
+        return b, r
+
+    def bandwidth_kernel_stats(self):
+        """{"bw_tick" | "bw_argmax" | "bw_gather": (total_ms, launches)} since
+        set_profiling(True)."""
+        lib = self._bandwidth_lib()
+        ms = np.zeros(len(_abi.BANDWIDTH_KERNEL_NAMES), dtype=np.float64)
+        cnt = np.zeros(len(_abi.BANDWIDTH_KERNEL_NAMES), dtype=np.int64)
+        _check(lib, lib.gs_read_bandwidth_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.BANDWIDTH_KERNEL_NAMES)}
 
     # ---------------------------------------------------------------- mesh reach
     def _mesh_reach_lib(self):
