@@ -108,6 +108,59 @@ struct DevScratch {
   ~DevScratch() { (void)hipFree(p); }
 };
 
+// The schedule of a periodic inspector (DESIGN.md §6n "The ticker"): every
+// `period` hops a tick goes into a ring of `cap` slots, tick k (k = 0, 1, ...)
+// when the hop counter becomes hopOf(k).  A read of tick k is valid while
+// taken - cap <= k < taken.  `what` prefixes the messages, `title` names the
+// option in the set-up refusals, `off` is said while it is not on.
+struct gs_engine;
+struct Ticker {
+  const char *what, *title, *off;
+  bool oneRank;  // not on a partitioned engine
+  bool on = false;
+  int64_t period = 0, taken = 0;
+  int cap = 0;
+  bool due(int64_t hop) const { return on && hop % period == 0; }
+  size_t slot() const { return (size_t)(taken % cap); }  // of the tick being taken
+  size_t slotOf(int64_t tick) const { return (size_t)(tick % cap); }
+  int64_t hopOf(int64_t tick) const { return (tick + 1) * period; }
+  int on_check() const {
+    if (on) return GS_OK;
+    gs_set_error(off);
+    return GS_ESTATE;
+  }
+  int64_t ticksTaken() const {  // (a negative GS_* code while off)
+    GS_TRY(on_check());
+    return taken;
+  }
+  int tickOk(int64_t tick) const {
+    GS_TRY(on_check());
+    if (tick < 0 || tick >= taken) {
+      gs_set_error(std::string(what) + ": tick " + std::to_string(tick) + " not taken yet (" + std::to_string(taken) +
+                   " so far)");
+      return GS_EINVAL;
+    }
+    if (tick < taken - cap) {
+      gs_set_error(std::string(what) + ": tick " + std::to_string(tick) + " already overwritten (ring of " +
+                   std::to_string(cap) + ")");
+      return GS_ESTATE;
+    }
+    return GS_OK;
+  }
+  // The refusals every gs_set_* of an inspector begins with, in their order;
+  // `c` is its config record (null: refused as a bad period).  Sets nothing:
+  // the caller arms the ticker once its own checks have passed too.
+  enum Needs : unsigned { kGossipsub = 1, kScoring = 2, kAccounting = 4 };
+  template <class Config>
+  int configure(const gs_engine* g, const Config* c, unsigned needs) const;
+  template <class Config>
+  void arm(const Config* c) {
+    period = c->period_hops;
+    cap = c->ticks;
+    on = true;
+  }
+};
+
 struct gs_engine {
   gs_config cfg{};
   gs_gossipsub_params gp{};
@@ -267,6 +320,19 @@ struct gs_engine {
     gs_set_error(std::string("device allocation failed (") + group + ")" + hint);
     return GS_ENOMEM;
   }
+  // A stage with a failure group of its own: a failure among the allocations
+  // `body` makes is reported here, under the group's name; an earlier stage's
+  // pending failure stays pending for that stage's allocFail.
+  template <class Body>
+  int allocGroup(const char* group, const char* hint, Body&& body) {
+    const bool before = allocFailed;
+    allocFailed = false;
+    body();
+    if (allocFailed) return allocFail(group, hint);
+    allocFailed = before;
+    return GS_OK;
+  }
+  unsigned cus = 1;  // the device's compute units (buildDevice): the capped grids are multiples of it
   // Per-edge device arrays (Dev::rxi): a sender-indexed array holds `rows`
   // values of the owned edges [e0, e1), a receiver-indexed one (outbox, fwdIn,
   // ibxRec) also the stage [e1, e1 + eOwn) on a partitioned rank; both through
@@ -407,83 +473,113 @@ struct gs_engine {
   }
   size_t traceOut = 0;
   int drainTrace();
+  // The observers below: each keeps what the caller configured, which outlives
+  // release(), apart from its `dev`: what start() allocates and derives, which
+  // release() forgets by assigning a fresh one.
+  //
   // latency statistics (gs_latency.h): the per-message and per-topic tables
   // ([S][bins] and [T][bins], bins = the largest age limit + 1; Dev::latCnt holds a hop's
   // counts) and the grid of k_lat_count
-  bool latOn = false;
-  uint32_t* dLatM = nullptr;
-  unsigned long long* dLatH = nullptr;
-  unsigned latGrid = 0;
+  struct {
+    bool on = false;
+    struct {
+      uint32_t* perMsg = nullptr;
+      unsigned long long* hist = nullptr;
+      unsigned grid = 0;
+    } dev;
+  } lat;
   int latBins() const { return ageMax + 1; }
-  // WithPeerScoreInspect (gs_inspect.h): a ring of inspCap ticks, each a row
+  // WithPeerScoreInspect (gs_inspect.h): a ring of ticks, each a row
   // (insp_row_len: score_hist, then mesh_deg), the sampled edges' scores and,
   // extended, their snapshot fields (k_inspect_gather's layout)
-  bool inspOn = false, inspExt = false;
-  int64_t inspPeriod = 0, inspTaken = 0;
-  int inspCap = 0;
-  std::vector<double> inspBounds;
-  std::vector<uint8_t> inspMask;     // [N] observers, or empty
-  std::vector<int64_t> inspEdges;    // the sampled edges of this rank, ascending
-  unsigned long long* dInspRows = nullptr;
-  double *dInspBounds = nullptr, *dInspScore = nullptr, *dInspExt = nullptr;
-  int64_t* dInspEdges = nullptr;
-  unsigned inspGrid = 0;
-  int inspRowLen() const { return insp_row_len((int)inspBounds.size(), T); }
-  size_t inspExtLen() const { return inspEdges.size() * (3 + 4 * (size_t)T); }  // 8-byte words per tick
+  struct {
+    Ticker tk{"score inspection", "peer score inspector", "score inspection is off (gs_set_score_inspect)", false};
+    bool ext = false;
+    std::vector<double> bounds;
+    std::vector<uint8_t> mask;     // [N] observers, or empty
+    struct {
+      std::vector<int64_t> edges;  // the sampled edges of this rank, ascending
+      unsigned long long* rows = nullptr;
+      double *bounds = nullptr, *score = nullptr, *ext = nullptr;
+      int64_t* edgeList = nullptr;
+      unsigned grid = 0;
+    } dev;
+  } insp;
+  int inspRowLen() const { return insp_row_len((int)insp.bounds.size(), T); }
+  size_t inspExtLen() const { return insp.dev.edges.size() * (3 + 4 * (size_t)T); }  // 8-byte words per tick
   // mesh health (gs_mesh_health.h): the label and size tables (uint32 [N][T]),
-  // a ring of meshCap rows (mesh_row_len), the batch's flags and the word count
-  bool meshOn = false, meshLabels = false;
-  int64_t meshPeriod = 0, meshTaken = 0;
-  int meshCap = 0;
-  std::vector<uint8_t> meshMask;     // [N] the hosts counted, or empty for all
-  uint8_t* dMeshMask = nullptr;
-  uint32_t *dMeshL = nullptr, *dMeshZ = nullptr, *dMeshFlag = nullptr;  // flags: [GS_MESH_BATCH + 1]
-  unsigned long long *dMeshRows = nullptr, *dMeshWords = nullptr;
-  unsigned meshGrid = 0;
-  int64_t meshIters = 0, meshBytes = 0;  // since the start or the last gs_set_profiling
+  // a ring of rows (mesh_row_len), the batch's flags and the word count
+  struct {
+    Ticker tk{"mesh health", "mesh health inspector", "mesh health is off (gs_set_mesh_health)", true};
+    bool labels = false;
+    std::vector<uint8_t> mask;     // [N] the hosts counted, or empty for all
+    int64_t iters = 0, bytes = 0;  // since the start or the last gs_set_profiling
+    struct {
+      uint8_t* mask = nullptr;
+      uint32_t *L = nullptr, *Z = nullptr, *flag = nullptr;  // flags: [GS_MESH_BATCH + 1]
+      unsigned long long *rows = nullptr, *words = nullptr;
+      unsigned grid = 0;
+    } dev;
+  } mesh;
   // mesh reach (gs_mesh_reach.h): the two bit tables (uint64 [N][T]), a ring of
-  // reachCap rows (reach_row_len), the members per topic, the batch's flags,
-  // the byte counters and, when asked for, the depth table (uint8 [K][N][T])
-  bool reachOn = false, reachDepths = false;
-  int64_t reachPeriod = 0, reachTaken = 0;
-  int reachCap = 0;
-  std::vector<int32_t> reachSrc;      // [K] the sources
-  std::vector<uint8_t> reachMask;     // [N] the hosts that can be targets, or empty for all
-  int32_t* dReachSrc = nullptr;
-  uint8_t *dReachMask = nullptr, *dReachDepths = nullptr;
-  uint64_t* dReachR[2] = {nullptr, nullptr};
-  uint32_t *dReachMembers = nullptr, *dReachFlag = nullptr;  // flags: [GS_REACH_BATCH + 1]
-  unsigned long long *dReachRows = nullptr, *dReachWords = nullptr;
-  unsigned reachGrid = 0;
-  int64_t reachPasses = 0, reachLevels = 0, reachBytes = 0;  // since the start or the last gs_set_profiling
+  // rows (reach_row_len), the members per topic, the batch's flags, the byte
+  // counters and, when asked for, the depth table (uint8 [K][N][T])
+  struct {
+    Ticker tk{"mesh reach", "mesh reach inspector", "mesh reach is off (gs_set_mesh_reach)", true};
+    bool depths = false;
+    std::vector<int32_t> src;      // [K] the sources
+    std::vector<uint8_t> mask;     // [N] the hosts that can be targets, or empty for all
+    int64_t passes = 0, levels = 0, bytes = 0;  // since the start or the last gs_set_profiling
+    struct {
+      int32_t* src = nullptr;
+      uint8_t *mask = nullptr, *depths = nullptr;
+      uint64_t* R[2] = {nullptr, nullptr};
+      uint32_t *members = nullptr, *flag = nullptr;  // flags: [GS_REACH_BATCH + 1]
+      unsigned long long *rows = nullptr, *words = nullptr;
+      unsigned grid = 0;
+    } dev;
+  } reach;
   // bandwidth statistics (gs_bandwidth.h): the per-node tables (uint64 [N][8]:
   // the cumulative sums at the previous tick, this tick's deltas), a ring of
-  // bwCap rows (bw_row_len) and the sampled nodes' values (k_bw_gather's layout)
-  bool bwOn = false;
-  int64_t bwPeriod = 0, bwTaken = 0;
-  int bwCap = 0;
-  std::vector<int64_t> bwBounds;
-  std::vector<int32_t> bwNodes;      // the sampled nodes, ascending
-  long long* dBwBounds = nullptr;
-  int32_t* dBwNodes = nullptr;
-  unsigned long long *dBwPrev = nullptr, *dBwDelta = nullptr, *dBwRows = nullptr, *dBwBytes = nullptr, *dBwRpcs = nullptr;
-  unsigned bwGrid = 0;
-  int bwRowLen() const { return bw_row_len((int)bwBounds.size()); }
+  // rows (bw_row_len) and the sampled nodes' values (k_bw_gather's layout)
+  struct {
+    Ticker tk{"bandwidth statistics", "bandwidth statistics",
+              "the bandwidth statistics are off (gs_set_bandwidth_stats)", true};
+    std::vector<int64_t> bounds;
+    std::vector<int32_t> nodes;    // the sampled nodes, ascending
+    struct {
+      long long* bounds = nullptr;
+      int32_t* nodes = nullptr;
+      unsigned long long *prev = nullptr, *delta = nullptr, *rows = nullptr, *bytes = nullptr, *rpcs = nullptr;
+      unsigned grid = 0;
+    } dev;
+  } bw;
+  int bwRowLen() const { return bw_row_len((int)bw.bounds.size()); }
+  // The tickers in the order their ticks run at the end of a hop (DESIGN.md
+  // §6p: mesh reach after the other two inspectors).
+  struct Tick {
+    Ticker* tk;
+    int (gs_engine::*take)();
+  };
+  const Tick tickers[4] = {{&insp.tk, &gs_engine::inspectTick},
+                           {&mesh.tk, &gs_engine::meshTick},
+                           {&reach.tk, &gs_engine::reachTick},
+                           {&bw.tk, &gs_engine::bandwidthTick}};
   // kernel timing: (kernel id, start event, end event) pending until a sync
   bool profiling = false;
   std::vector<hipEvent_t> evPool;
   size_t evUsed = 0;
   std::vector<int> pendKid;
-  // (past the public kernel ids: the latency kernels, gs_read_latency_kernel_stats, and the
-  // inspection's three passes, gs_read_inspect_kernel_stats; mesh health's four,
-  // gs_read_mesh_health_kernel_stats; mesh reach's four, gs_read_mesh_reach_kernel_stats; the
-  // bandwidth statistics' three, gs_read_bandwidth_kernel_stats)
-  static constexpr int kLatCount = GS_NUM_KERNELS, kLatFold = GS_NUM_KERNELS + 1;
-  static constexpr int kInspScore = GS_NUM_KERNELS + 2, kInspReduce = GS_NUM_KERNELS + 3;
-  static constexpr int kInspGather = GS_NUM_KERNELS + 4, kMeshInit = GS_NUM_KERNELS + 5;
-  static constexpr int kReachMembers = kMeshInit + 4;  // (kMeshInit + GS_MESH_K_*)
-  static constexpr int kBwTick = kReachMembers + 4;    // (kReachMembers + GS_REACH_K_*)
-  static constexpr int kTimed = kBwTick + GS_BW_NUM_STATS;  // (kBwTick + GS_BW_K_*)
+  // Past the public kernel ids, each feature's range follows the one before it:
+  // the latency kernels (gs_read_latency_kernel_stats), the inspection's three
+  // passes (gs_read_inspect_kernel_stats), then kMeshInit + GS_MESH_K_*,
+  // kReachMembers + GS_REACH_K_* and kBwTick + GS_BW_K_* (their gs_read_*_kernel_stats)
+  enum : int { kLatCount = GS_NUM_KERNELS, kLatFold, kLatEnd };
+  enum : int { kInspScore = kLatEnd, kInspReduce, kInspGather, kInspEnd };
+  static constexpr int kMeshInit = kInspEnd;
+  static constexpr int kReachMembers = kMeshInit + GS_MESH_ST_ITERS;
+  static constexpr int kBwTick = kReachMembers + GS_REACH_ST_PASSES;
+  static constexpr int kTimed = kBwTick + GS_BW_NUM_STATS;
   double kMs[kTimed] = {0};
   int64_t kLaunches[kTimed] = {0};
   hipEvent_t nextEvent() {
@@ -569,27 +665,12 @@ struct gs_engine {
     stream = nullptr;
     d = Dev{};
     dDev = nullptr;
-    dLatM = nullptr;
-    dLatH = nullptr;
-    dInspRows = nullptr;
-    dInspBounds = dInspScore = dInspExt = nullptr;
-    dInspEdges = nullptr;
-    inspEdges.clear();
-    inspTaken = 0;
-    dMeshMask = nullptr;
-    dMeshL = dMeshZ = dMeshFlag = nullptr;
-    dMeshRows = dMeshWords = nullptr;
-    meshTaken = 0;
-    dReachSrc = nullptr;
-    dReachMask = dReachDepths = nullptr;
-    dReachR[0] = dReachR[1] = nullptr;
-    dReachMembers = dReachFlag = nullptr;
-    dReachRows = dReachWords = nullptr;
-    reachTaken = 0;
-    dBwBounds = nullptr;
-    dBwNodes = nullptr;
-    dBwPrev = dBwDelta = dBwRows = dBwBytes = dBwRpcs = nullptr;
-    bwTaken = 0;
+    lat.dev = {};
+    insp.dev = {};
+    mesh.dev = {};
+    reach.dev = {};
+    bw.dev = {};
+    for (const Tick& t : tickers) t.tk->taken = 0;
     started = churnOn = allocFailed = false;
     uploaded = 0;
     aliveH.clear();
@@ -664,6 +745,35 @@ struct gs_engine {
   int allocMeshHealth(), meshTick();
   int allocMeshReach(), reachTick();
   int allocBandwidth(), bandwidthTick();
+  // A fixed point bounded on the host (DESIGN.md §6n "The fixed-point driver"):
+  // iterations go out in batches of `batch`, launch(i, ran) issuing the batch's
+  // iteration i against dFlag + i (`ran`: the iterations that ran before this
+  // batch).  An iteration runs if its flag is set and sets the next one if it
+  // changed anything; the batch's first flag is set here.  After a batch the
+  // host reads the flags: flag[i] != 0 counts iteration i as run, the flag
+  // past the batch's last clear ends the loop.  More than `limit` iterations
+  // fail with failText, *ran, failUnit and the hop.
+  template <class Launch>
+  int runBatched(int batch, uint32_t* dFlag, int64_t limit, const char* failText, const char* failUnit,
+                 Launch&& launch, int64_t* ran) {
+    std::vector<uint32_t> flag((size_t)batch + 1);
+    *ran = 0;
+    for (bool ended = false; !ended;) {
+      const int n = (int)std::min<int64_t>(batch, limit - *ran);
+      if (n <= 0) {
+        gs_set_error(failText + std::to_string(*ran) + failUnit + " (hop " + std::to_string(hop) + ")");
+        return GS_EDEVICE;
+      }
+      HIPCHECK(hipMemsetAsync(dFlag, 0, flag.size() * 4, stream));
+      HIPCHECK(hipMemsetAsync(dFlag, 1, 4, stream));  // non-zero: the batch's first iteration runs
+      for (int i = 0; i < n; ++i) launch(i, *ran);
+      HIPCHECK(hipMemcpyAsync(flag.data(), dFlag, flag.size() * 4, hipMemcpyDeviceToHost, stream));
+      HIPCHECK(hipStreamSynchronize(stream));
+      for (int i = 0; i < n; ++i) *ran += flag[i] != 0u;
+      ended = flag[n] == 0u;
+    }
+    return GS_OK;
+  }
   void refreshOrFold(const Hop& hp), heartbeat(const Hop& hp);
   template <bool ADV>
   PhaseADev<ADV> phaseADev() const {
@@ -683,3 +793,22 @@ struct gs_engine {
   int deviceErrorCode(int32_t err);
   int deviceErrorText(int32_t err, int64_t atHop);
 };
+
+template <class Config>
+int Ticker::configure(const gs_engine* g, const Config* c, unsigned needs) const {
+  const auto refuse = [](const std::string& text, int code) {
+    gs_set_error(text);
+    return code;
+  };
+  const std::string w = what, t = title;
+  if (g->started) return refuse("the " + t + " must be set before the first step", GS_ESTATE);
+  if (on) return refuse("duplicate " + t, GS_ESTATE);
+  if ((needs & kGossipsub) && g->cfg.router != GS_ROUTER_GOSSIPSUB)
+    return refuse("pubsub router is not gossipsub", GS_EUNSUPPORTED);
+  if ((needs & kScoring) && !g->scoring) return refuse("peer scoring is not enabled", GS_EUNSUPPORTED);
+  if ((needs & kAccounting) && !g->acctOn) return refuse(w + ": RPC accounting is off", GS_ESTATE);
+  if (oneRank && g->world > 1) return refuse(w + ": not on a partitioned engine", GS_EUNSUPPORTED);
+  if (!c || c->period_hops <= 0) return refuse(w + ": period_hops must be positive", GS_EINVAL);
+  if (c->ticks < 1) return refuse(w + ": ticks must be at least 1", GS_EINVAL);
+  return GS_OK;
+}

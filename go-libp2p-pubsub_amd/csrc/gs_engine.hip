@@ -161,6 +161,9 @@ int gs_engine::start() {
 int gs_engine::buildDevice(const Plan& pl) {
   HIPCHECK(hipSetDevice(cfg.device));
   HIPCHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  int n = 0;
+  HIPCHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, cfg.device));
+  cus = (unsigned)std::max(n, 1);
   dDev = dalloc<Dev>(1);
   GS_TRY(allocFail("Dev record"));
   setDevScalars(pl);
@@ -686,17 +689,15 @@ int gs_engine::allocReadback() {
 // Latency statistics (gs_latency.h), at their exact sizes: S + S * bins
 // uint32 and T * bins uint64.
 int gs_engine::allocLatency() {
-  if (!latOn) return GS_OK;
+  if (!lat.on) return GS_OK;
   const size_t bins = (size_t)latBins();
   d.latCnt = dalloc<uint32_t>((size_t)S);
-  dLatM = dalloc<uint32_t>((size_t)S * bins);
-  dLatH = dalloc<unsigned long long>((size_t)T * bins);
-  int cus = 0;
-  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
+  lat.dev.perMsg = dalloc<uint32_t>((size_t)S * bins);
+  lat.dev.hist = dalloc<unsigned long long>((size_t)T * bins);
   // k_lat_count's grid: as many workgroups per CU as its LDS holds of their 4 S byte tables,
   // GS_LAT_WGS_PER_CU at the most (a workgroup that is not resident only runs as a tail)
   const unsigned fit = (unsigned)(GS_LAT_CU_LDS / std::max<size_t>((size_t)S * 4, 1));
-  latGrid = std::min<unsigned>(std::max(fit, 1u), GS_LAT_WGS_PER_CU) * (unsigned)std::max(cus, 1);
+  lat.dev.grid = std::min<unsigned>(std::max(fit, 1u), GS_LAT_WGS_PER_CU) * cus;
   return GS_OK;
 }
 
@@ -704,32 +705,29 @@ int gs_engine::allocLatency() {
 // owned observers, ascending), the ring at its exact size and
 // k_inspect_reduce's grid.
 int gs_engine::allocInspect() {
-  if (!inspOn) return GS_OK;
-  inspEdges.clear();
-  if (!inspMask.empty())
+  if (!insp.tk.on) return GS_OK;
+  auto& v = insp.dev;
+  v.edges.clear();
+  if (!insp.mask.empty())
     for (int u = n0; u < n1; ++u)
-      if (inspMask[u])
-        for (int64_t e = rowptr[u]; e < rowptr[u + 1]; ++e) inspEdges.push_back(e);
-  const size_t nS = inspEdges.size(), cap = (size_t)inspCap, nb = inspBounds.size();
-  const bool before = allocFailed;
-  allocFailed = false;
-  dInspRows = dalloc<unsigned long long>(cap * (size_t)inspRowLen());
-  dInspBounds = dalloc<double>(std::max<size_t>(nb, 1));
-  if (nS) {
-    dInspEdges = dalloc<int64_t>(nS);
-    dInspScore = dalloc<double>(cap * nS);
-    if (inspExt) dInspExt = dalloc<double>(cap * inspExtLen());
-  }
-  if (allocFailed) return allocFail("score inspection ring", "; reduce ticks or the sampled nodes");
-  allocFailed = before;
-  GS_TRY(put(dInspBounds, inspBounds.data(), nb));
-  GS_TRY(putNow(dInspEdges, inspEdges.data(), nS));
-  int cus = 0;
-  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
+      if (insp.mask[u])
+        for (int64_t e = rowptr[u]; e < rowptr[u + 1]; ++e) v.edges.push_back(e);
+  const size_t nS = v.edges.size(), cap = (size_t)insp.tk.cap, nb = insp.bounds.size();
+  GS_TRY(allocGroup("score inspection ring", "; reduce ticks or the sampled nodes", [&] {
+    v.rows = dalloc<unsigned long long>(cap * (size_t)inspRowLen());
+    v.bounds = dalloc<double>(std::max<size_t>(nb, 1));
+    if (nS) {
+      v.edgeList = dalloc<int64_t>(nS);
+      v.score = dalloc<double>(cap * nS);
+      if (insp.ext) v.ext = dalloc<double>(cap * inspExtLen());
+    }
+  }));
+  GS_TRY(put(v.bounds, insp.bounds.data(), nb));
+  GS_TRY(putNow(v.edgeList, v.edges.data(), nS));
   // k_inspect_reduce's grid: as many workgroups per CU as its LDS holds of their tables,
   // GS_INSP_WGS_PER_CU at the most (a workgroup that is not resident only runs as a tail)
   const unsigned fit = (unsigned)(GS_INSP_CU_LDS / insp_lds_bytes((int)nb, T));
-  inspGrid = std::min<unsigned>(std::max(fit, 1u), GS_INSP_WGS_PER_CU) * (unsigned)std::max(cus, 1);
+  v.grid = std::min<unsigned>(std::max(fit, 1u), GS_INSP_WGS_PER_CU) * cus;
   return GS_OK;
 }
 
@@ -737,24 +735,24 @@ int gs_engine::allocInspect() {
 // gs_read_scores computes them, then the row and the sampled edges into the
 // tick's ring slot.  Nothing is read back: the host knows a tick's hop.
 int gs_engine::inspectTick() {
-  const int slot = (int)(inspTaken % inspCap);
-  const int nb = (int)inspBounds.size();
-  const int64_t nS = (int64_t)inspEdges.size();
-  unsigned long long* row = dInspRows + (size_t)slot * inspRowLen();
+  const auto& v = insp.dev;
+  const size_t slot = insp.tk.slot();
+  const int nb = (int)insp.bounds.size();
+  const int64_t nS = (int64_t)v.edges.size();
+  unsigned long long* row = v.rows + slot * inspRowLen();
   HIPCHECK(hipMemsetAsync(row, 0, (size_t)inspRowLen() * 8, stream));
   TIMED(this, kInspScore, (score_rows<0>(d, eOwn, T, dScoreTmp, stream)));
   if (nOwn()) {
-    const unsigned grid = std::min(inspGrid, nblk(nOwn(), GS_INSP_BLOCK / 64));
+    const unsigned grid = std::min(v.grid, nblk(nOwn(), GS_INSP_BLOCK / 64));
     TIMED(this, kInspReduce, (k_inspect_reduce<<<grid, GS_INSP_BLOCK, insp_row_lds(nb, T), stream>>>(
-                                 d, dScoreTmp, dInspBounds, nb, row)));
+                                 d, dScoreTmp, v.bounds, nb, row)));
   }
   if (nS) {
-    double* ext = inspExt ? dInspExt + (size_t)slot * inspExtLen() : nullptr;
+    double* ext = insp.ext ? v.ext + slot * inspExtLen() : nullptr;
     TIMED(this, kInspGather, (k_inspect_gather<<<nblk(nS * T, 256), 256, 0, stream>>>(
-                                 d, dInspEdges, nS, dScoreTmp, dInspScore + (size_t)slot * nS, ext)));
+                                 d, v.edgeList, nS, dScoreTmp, v.score + slot * nS, ext)));
   }
   HIPCHECK(hipGetLastError());
-  inspTaken++;
   return GS_OK;
 }
 
@@ -762,81 +760,61 @@ int gs_engine::inspectTick() {
 // ring of rows, the include mask, a batch's flags and the word counter; the
 // grid of the three node passes.
 int gs_engine::allocMeshHealth() {
-  if (!meshOn) return GS_OK;
+  if (!mesh.tk.on) return GS_OK;
+  auto& v = mesh.dev;
   const size_t nt = (size_t)N * (size_t)T;
-  const bool before = allocFailed;
-  allocFailed = false;
-  dMeshL = dalloc<uint32_t>(nt);
-  dMeshZ = dalloc<uint32_t>(nt);
-  dMeshRows = dalloc<unsigned long long>((size_t)meshCap * (size_t)mesh_row_len(T));
-  dMeshFlag = dalloc<uint32_t>(GS_MESH_BATCH + 1);
-  dMeshWords = dalloc<unsigned long long>(1);
-  if (!meshMask.empty()) dMeshMask = dalloc<uint8_t>((size_t)N);
-  if (allocFailed) return allocFail("mesh health tables", "; reduce ticks or num_nodes");
-  allocFailed = before;
-  GS_TRY(putNow(dMeshMask, meshMask.data(), meshMask.size()));
-  int cus = 0;
-  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
-  meshGrid = std::min<unsigned>(GS_MESH_WGS_PER_CU * (unsigned)std::max(cus, 1),
-                                std::max(nblk(mesh_groups(N, T), GS_MESH_BLOCK / 64), 1u));
+  GS_TRY(allocGroup("mesh health tables", "; reduce ticks or num_nodes", [&] {
+    v.L = dalloc<uint32_t>(nt);
+    v.Z = dalloc<uint32_t>(nt);
+    v.rows = dalloc<unsigned long long>((size_t)mesh.tk.cap * (size_t)mesh_row_len(T));
+    v.flag = dalloc<uint32_t>(GS_MESH_BATCH + 1);
+    v.words = dalloc<unsigned long long>(1);
+    if (!mesh.mask.empty()) v.mask = dalloc<uint8_t>((size_t)N);
+  }));
+  GS_TRY(putNow(v.mask, mesh.mask.data(), mesh.mask.size()));
+  v.grid = std::min<unsigned>(GS_MESH_WGS_PER_CU * cus, std::max(nblk(mesh_groups(N, T), GS_MESH_BLOCK / 64), 1u));
   return GS_OK;
 }
 
 // A tick at the end of a hop (`hop` already counts it): labels to their fixed
-// point in batches of GS_MESH_BATCH iterations, the host reading the batch's
-// flags in between (flag[i] != 0: iteration i of the batch had work and ran;
-// the last flag 0: the labels have settled), at most N iterations in all; then
-// the sizes and the row.  The byte count: what every pass streams, from the
-// shapes, plus the label words the kernels counted.
+// point in batches of GS_MESH_BATCH iterations (runBatched: an iteration that
+// had work ran; the labels have settled when one lowers nothing), at most N
+// iterations in all; then the sizes and the row.  The byte count: what every
+// pass streams, from the shapes, plus the label words the kernels counted.
 int gs_engine::meshTick() {
-  unsigned long long* row = dMeshRows + (size_t)(meshTaken % meshCap) * (size_t)mesh_row_len(T);
+  const auto& v = mesh.dev;
+  unsigned long long* row = v.rows + mesh.tk.slot() * (size_t)mesh_row_len(T);
   const int64_t nt = (int64_t)N * T;
   const bool wide = mesh_tp(T) == 64;
   HIPCHECK(hipMemsetAsync(row, 0, (size_t)mesh_row_len(T) * 8, stream));
-  HIPCHECK(hipMemsetAsync(dMeshWords, 0, 8, stream));
-  TIMED(this, kMeshInit + GS_MESH_K_INIT,
-        (k_mesh_init<<<nblk(nt, 256), 256, 0, stream>>>(d, dMeshMask, dMeshL, dMeshZ)));
+  HIPCHECK(hipMemsetAsync(v.words, 0, 8, stream));
+  TIMED(this, kMeshInit + GS_MESH_K_INIT, (k_mesh_init<<<nblk(nt, 256), 256, 0, stream>>>(d, v.mask, v.L, v.Z)));
   int64_t iters = 0;
-  for (bool settled = false; !settled;) {
-    const int n = (int)std::min<int64_t>(GS_MESH_BATCH, (int64_t)N - iters);
-    if (n <= 0) {
-      gs_set_error("mesh health: labels did not converge after " + std::to_string(iters) + " iterations (hop " +
-                   std::to_string(hop) + ")");
-      return GS_EDEVICE;
-    }
-    HIPCHECK(hipMemsetAsync(dMeshFlag, 0, (size_t)(GS_MESH_BATCH + 1) * 4, stream));
-    HIPCHECK(hipMemsetAsync(dMeshFlag, 1, 4, stream));  // non-zero: the batch's first iteration runs
-    for (int i = 0; i < n; ++i)
-      with_consts([&](auto w) {
-        TIMED(this, kMeshInit + GS_MESH_K_LABEL,
-              (k_mesh_label<CV(w)><<<meshGrid, GS_MESH_BLOCK, 0, stream>>>(d, dMeshL, dMeshFlag + i, dMeshWords)));
-      }, Flag{wide});
-    uint32_t flag[GS_MESH_BATCH + 1];
-    HIPCHECK(hipMemcpyAsync(flag, dMeshFlag, sizeof flag, hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
-    for (int i = 0; i < n; ++i) iters += flag[i] != 0u;
-    settled = flag[n] == 0u;
-  }
-  TIMED(this, kMeshInit + GS_MESH_K_SIZES,
-        (k_mesh_sizes<<<meshGrid, GS_MESH_BLOCK, 0, stream>>>(d, dMeshL, dMeshZ, dMeshWords)));
+  GS_TRY(runBatched(GS_MESH_BATCH, v.flag, N, "mesh health: labels did not converge after ", " iterations",
+                    [&](int i, int64_t) {
+                      with_consts([&](auto w) {
+                        TIMED(this, kMeshInit + GS_MESH_K_LABEL,
+                              (k_mesh_label<CV(w)><<<v.grid, GS_MESH_BLOCK, 0, stream>>>(d, v.L, v.flag + i, v.words)));
+                      }, Flag{wide});
+                    }, &iters));
+  TIMED(this, kMeshInit + GS_MESH_K_SIZES, (k_mesh_sizes<<<v.grid, GS_MESH_BLOCK, 0, stream>>>(d, v.L, v.Z, v.words)));
   with_consts([&](auto w) {
     TIMED(this, kMeshInit + GS_MESH_K_ROW,
-          (k_mesh_row<CV(w)><<<meshGrid, GS_MESH_BLOCK, 0, stream>>>(d, dMeshMask, dMeshL, dMeshZ, row)));
+          (k_mesh_row<CV(w)><<<v.grid, GS_MESH_BLOCK, 0, stream>>>(d, v.mask, v.L, v.Z, row)));
   }, Flag{wide});
   HIPCHECK(hipGetLastError());
   unsigned long long words = 0;
-  HIPCHECK(hipMemcpyAsync(&words, dMeshWords, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHECK(hipMemcpyAsync(&words, v.words, 8, hipMemcpyDeviceToHost, stream));
   HIPCHECK(hipStreamSynchronize(stream));
   // per edge: mesh word, reverse edge, peer, the reverse edge's mesh word (the
   // row pass: the peer's include byte too); per node: its CSR row bounds
   const int64_t edgeWalk = E * (8 + 4 + 4 + 8) + (int64_t)N * 8;
-  meshIters += iters;
-  meshBytes += nt * 8 + (int64_t)N * 10          // init: two stores; the subscription word, router and include bytes
-               + iters * (edgeWalk + nt * 4)     // an iteration: the edges and the nodes' own labels
-               + nt * 4                          // sizes: every label
-               + nt * 4 + edgeWalk + E           // row: every label, the edges
-               + (int64_t)words * 4;             // what the label and size passes counted besides
-  meshTaken++;
+  mesh.iters += iters;
+  mesh.bytes += nt * 8 + (int64_t)N * 10          // init: two stores; the subscription word, router and include bytes
+                + iters * (edgeWalk + nt * 4)     // an iteration: the edges and the nodes' own labels
+                + nt * 4                          // sizes: every label
+                + nt * 4 + edgeWalk + E           // row: every label, the edges
+                + (int64_t)words * 4;             // what the label and size passes counted besides
   return GS_OK;
 }
 
@@ -845,27 +823,24 @@ int gs_engine::meshTick() {
 // sampled nodes' values; k_bw_tick's grid.  After allocAcct: the counters
 // start at zero, as the hello packets are overhead.
 int gs_engine::allocBandwidth() {
-  if (!bwOn) return GS_OK;
-  const size_t nS = bwNodes.size(), cap = (size_t)bwCap, nb = bwBounds.size();
-  const bool before = allocFailed;
-  allocFailed = false;
-  d.bwX = ealloc<unsigned long long>(0, 2);
-  dBwPrev = dalloc<unsigned long long>((size_t)N * GS_BW_NODE_WORDS);
-  dBwDelta = dalloc<unsigned long long>((size_t)N * GS_BW_NODE_WORDS);
-  dBwRows = dalloc<unsigned long long>(cap * (size_t)bwRowLen());
-  dBwBounds = dalloc<long long>(std::max<size_t>(nb, 1));
-  if (nS) {
-    dBwNodes = dalloc<int32_t>(nS);
-    dBwBytes = dalloc<unsigned long long>(cap * nS * GS_BW_NODE_WORDS);
-    dBwRpcs = dalloc<unsigned long long>(cap * nS * GS_BW_DIRS);
-  }
-  if (allocFailed) return allocFail("bandwidth statistics", "; reduce ticks or the sampled nodes");
-  allocFailed = before;
-  GS_TRY(put(dBwBounds, reinterpret_cast<const long long*>(bwBounds.data()), nb));
-  GS_TRY(putNow(dBwNodes, bwNodes.data(), nS));
-  int cus = 0;
-  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
-  bwGrid = GS_BW_WGS_PER_CU * (unsigned)std::max(cus, 1);
+  if (!bw.tk.on) return GS_OK;
+  auto& v = bw.dev;
+  const size_t nS = bw.nodes.size(), cap = (size_t)bw.tk.cap, nb = bw.bounds.size();
+  GS_TRY(allocGroup("bandwidth statistics", "; reduce ticks or the sampled nodes", [&] {
+    d.bwX = ealloc<unsigned long long>(0, 2);
+    v.prev = dalloc<unsigned long long>((size_t)N * GS_BW_NODE_WORDS);
+    v.delta = dalloc<unsigned long long>((size_t)N * GS_BW_NODE_WORDS);
+    v.rows = dalloc<unsigned long long>(cap * (size_t)bwRowLen());
+    v.bounds = dalloc<long long>(std::max<size_t>(nb, 1));
+    if (nS) {
+      v.nodes = dalloc<int32_t>(nS);
+      v.bytes = dalloc<unsigned long long>(cap * nS * GS_BW_NODE_WORDS);
+      v.rpcs = dalloc<unsigned long long>(cap * nS * GS_BW_DIRS);
+    }
+  }));
+  GS_TRY(put(v.bounds, reinterpret_cast<const long long*>(bw.bounds.data()), nb));
+  GS_TRY(putNow(v.nodes, bw.nodes.data(), nS));
+  v.grid = GS_BW_WGS_PER_CU * cus;
   return GS_OK;
 }
 
@@ -873,25 +848,24 @@ int gs_engine::allocBandwidth() {
 // sampled nodes into the tick's ring slot.  Nothing is read back: the host
 // knows a tick's hop.
 int gs_engine::bandwidthTick() {
-  const int slot = (int)(bwTaken % bwCap);
-  const int64_t nS = (int64_t)bwNodes.size();
-  unsigned long long* row = dBwRows + (size_t)slot * bwRowLen();
+  const auto& v = bw.dev;
+  const size_t slot = bw.tk.slot();
+  const int64_t nS = (int64_t)bw.nodes.size();
+  unsigned long long* row = v.rows + slot * bwRowLen();
   HIPCHECK(hipMemsetAsync(row, 0, (size_t)bwRowLen() * 8, stream));
   HIPCHECK(hipMemsetAsync(row + GS_BW_ROW_ARG, 0xFF, (size_t)GS_BW_DIRS * GS_BW_CLASSES * 8, stream));  // -1: no node
   if (nOwn()) {
-    const unsigned grid = std::min(bwGrid, nblk(nOwn(), GS_BW_BLOCK / 64));
+    const unsigned grid = std::min(v.grid, nblk(nOwn(), GS_BW_BLOCK / 64));
     TIMED(this, kBwTick + GS_BW_K_TICK, (k_bw_tick<<<grid, GS_BW_BLOCK, 0, stream>>>(
-                                            d, dBwBounds, (int)bwBounds.size(), dBwPrev, dBwDelta, row)));
+                                            d, v.bounds, (int)bw.bounds.size(), v.prev, v.delta, row)));
     TIMED(this, kBwTick + GS_BW_K_ARGMAX,
-          (k_bw_argmax<<<nblk((int64_t)nOwn() * GS_BW_NODE_WORDS, 256), 256, 0, stream>>>(d, dBwDelta, row)));
+          (k_bw_argmax<<<nblk((int64_t)nOwn() * GS_BW_NODE_WORDS, 256), 256, 0, stream>>>(d, v.delta, row)));
   }
   if (nS)
     TIMED(this, kBwTick + GS_BW_K_GATHER,
           (k_bw_gather<<<nblk(nS * GS_BW_NODE_WORDS, 256), 256, 0, stream>>>(
-              dBwNodes, nS, dBwDelta, dBwBytes + (size_t)slot * nS * GS_BW_NODE_WORDS,
-              dBwRpcs + (size_t)slot * nS * GS_BW_DIRS)));
+              v.nodes, nS, v.delta, v.bytes + slot * nS * GS_BW_NODE_WORDS, v.rpcs + slot * nS * GS_BW_DIRS)));
   HIPCHECK(hipGetLastError());
-  bwTaken++;
   return GS_OK;
 }
 
@@ -900,50 +874,46 @@ int gs_engine::bandwidthTick() {
 // flags, the byte counters and, when asked for, the depth table; the grid of
 // the node passes (mesh health's).
 int gs_engine::allocMeshReach() {
-  if (!reachOn) return GS_OK;
-  const size_t nt = (size_t)N * (size_t)T, K = reachSrc.size();
-  const bool before = allocFailed;
-  allocFailed = false;
-  dReachR[0] = dalloc<uint64_t>(nt);
-  dReachR[1] = dalloc<uint64_t>(nt);
-  dReachRows = dalloc<unsigned long long>((size_t)reachCap * (size_t)reach_row_len((int)K, T));
-  dReachSrc = dalloc<int32_t>(K);
-  dReachMembers = dalloc<uint32_t>((size_t)T);
-  dReachFlag = dalloc<uint32_t>(GS_REACH_BATCH + 1);
-  dReachWords = dalloc<unsigned long long>(GS_REACH_W_NUM);
-  if (!reachMask.empty()) dReachMask = dalloc<uint8_t>((size_t)N);
-  if (reachDepths) dReachDepths = dalloc<uint8_t>(K * nt, 0xFF);
-  if (allocFailed) return allocFail("mesh reach tables", "; reduce ticks, num_sources or num_nodes, or drop depths");
-  allocFailed = before;
-  GS_TRY(put(dReachSrc, reachSrc.data(), K));
-  GS_TRY(putNow(dReachMask, reachMask.data(), reachMask.size()));
-  int cus = 0;
-  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device));
-  reachGrid = std::min<unsigned>(GS_MESH_WGS_PER_CU * (unsigned)std::max(cus, 1),
-                                 std::max(nblk(mesh_groups(N, T), GS_MESH_BLOCK / 64), 1u));
+  if (!reach.tk.on) return GS_OK;
+  auto& v = reach.dev;
+  const size_t nt = (size_t)N * (size_t)T, K = reach.src.size();
+  GS_TRY(allocGroup("mesh reach tables", "; reduce ticks, num_sources or num_nodes, or drop depths", [&] {
+    v.R[0] = dalloc<uint64_t>(nt);
+    v.R[1] = dalloc<uint64_t>(nt);
+    v.rows = dalloc<unsigned long long>((size_t)reach.tk.cap * (size_t)reach_row_len((int)K, T));
+    v.src = dalloc<int32_t>(K);
+    v.members = dalloc<uint32_t>((size_t)T);
+    v.flag = dalloc<uint32_t>(GS_REACH_BATCH + 1);
+    v.words = dalloc<unsigned long long>(GS_REACH_W_NUM);
+    if (!reach.mask.empty()) v.mask = dalloc<uint8_t>((size_t)N);
+    if (reach.depths) v.depths = dalloc<uint8_t>(K * nt, 0xFF);
+  }));
+  GS_TRY(put(v.src, reach.src.data(), K));
+  GS_TRY(putNow(v.mask, reach.mask.data(), reach.mask.size()));
+  v.grid = std::min<unsigned>(GS_MESH_WGS_PER_CU * cus, std::max(nblk(mesh_groups(N, T), GS_MESH_BLOCK / 64), 1u));
   return GS_OK;
 }
 
 // A tick at the end of a hop (`hop` already counts it), after the other
 // inspectors': the members once, then a pass per 64 sources.  A pass clears R0,
-// sets its sources' bits and runs the levels in batches of GS_REACH_BATCH,
-// level L reading R[(L - 1) & 1] and writing R[L & 1]; the host reads the
-// batch's flags in between (flag[i] != 0: level i of the batch ran; the last
-// flag 0: the level before set nothing, the search has ended), at most N levels
-// per pass.  The byte count: what every kernel streams, from the shapes, plus
-// what the level kernel counted.
+// sets its sources' bits and runs the levels in batches of GS_REACH_BATCH
+// (runBatched: the search has ended when a level sets nothing), level L reading
+// R[(L - 1) & 1] and writing R[L & 1], at most N levels per pass.  The byte
+// count: what every kernel streams, from the shapes, plus what the level
+// kernel counted.
 int gs_engine::reachTick() {
-  const int K = (int)reachSrc.size();
+  const auto& v = reach.dev;
+  const int K = (int)reach.src.size();
   const int64_t nt = (int64_t)N * T;
-  unsigned long long* row = dReachRows + (size_t)(reachTaken % reachCap) * (size_t)reach_row_len(K, T);
+  unsigned long long* row = v.rows + reach.tk.slot() * (size_t)reach_row_len(K, T);
   unsigned long long* hist = row + (size_t)K * T * GS_REACH_ROW_FIELDS;
   const bool wide = mesh_tp(T) == 64;
   HIPCHECK(hipMemsetAsync(row, 0, (size_t)reach_row_len(K, T) * 8, stream));
-  HIPCHECK(hipMemsetAsync(dReachWords, 0, GS_REACH_W_NUM * 8, stream));
-  HIPCHECK(hipMemsetAsync(dReachMembers, 0, (size_t)T * 4, stream));
-  if (reachDepths) HIPCHECK(hipMemsetAsync(dReachDepths, 0xFF, (size_t)K * (size_t)nt, stream));
+  HIPCHECK(hipMemsetAsync(v.words, 0, GS_REACH_W_NUM * 8, stream));
+  HIPCHECK(hipMemsetAsync(v.members, 0, (size_t)T * 4, stream));
+  if (reach.depths) HIPCHECK(hipMemsetAsync(v.depths, 0xFF, (size_t)K * (size_t)nt, stream));
   TIMED(this, kReachMembers + GS_REACH_K_MEMBERS,
-        (k_reach_members<<<reachGrid, GS_MESH_BLOCK, 0, stream>>>(d, dReachMask, dReachMembers)));
+        (k_reach_members<<<v.grid, GS_MESH_BLOCK, 0, stream>>>(d, v.mask, v.members)));
   int64_t levels = 0;
   int passes = 0;
   for (int k0 = 0; k0 < K; k0 += 64, ++passes) {
@@ -951,55 +921,40 @@ int gs_engine::reachTick() {
     const uint64_t full = ns == 64 ? ~0ull : (1ull << ns) - 1ull;
     unsigned long long* prow = row + (size_t)k0 * T * GS_REACH_ROW_FIELDS;
     unsigned long long* phist = hist + (size_t)k0 * T * GS_REACH_DEPTH_BINS;
-    uint8_t* pdepths = reachDepths ? dReachDepths + (size_t)k0 * (size_t)nt : nullptr;
-    HIPCHECK(hipMemsetAsync(dReachR[0], 0, (size_t)nt * 8, stream));
+    uint8_t* pdepths = reach.depths ? v.depths + (size_t)k0 * (size_t)nt : nullptr;
+    HIPCHECK(hipMemsetAsync(v.R[0], 0, (size_t)nt * 8, stream));
     TIMED(this, kReachMembers + GS_REACH_K_INIT,
-          (k_reach_init<<<nblk((int64_t)ns * T, 256), 256, 0, stream>>>(d, dReachSrc + k0, ns, dReachR[0], pdepths)));
+          (k_reach_init<<<nblk((int64_t)ns * T, 256), 256, 0, stream>>>(d, v.src + k0, ns, v.R[0], pdepths)));
     int64_t ran = 0;
-    for (bool ended = false; !ended;) {
-      const int n = (int)std::min<int64_t>(GS_REACH_BATCH, (int64_t)N - ran);
-      if (n <= 0) {
-        gs_set_error("mesh reach: levels did not end after " + std::to_string(ran) + " (hop " + std::to_string(hop) +
-                     ")");
-        return GS_EDEVICE;
-      }
-      HIPCHECK(hipMemsetAsync(dReachFlag, 0, (size_t)(GS_REACH_BATCH + 1) * 4, stream));
-      HIPCHECK(hipMemsetAsync(dReachFlag, 1, 4, stream));  // non-zero: the batch's first level runs
-      for (int i = 0; i < n; ++i) {
-        const int level = (int)ran + i + 1;  // (a launch past the search's end returns at once: its level is not used)
-        with_consts([&](auto w) {
-          TIMED(this, kReachMembers + GS_REACH_K_LEVEL,
-                (k_reach_level<CV(w)><<<reachGrid, GS_MESH_BLOCK, 0, stream>>>(
-                    d, dReachMask, dReachR[(level - 1) & 1], dReachR[level & 1], full, level, dReachFlag + i, prow,
-                    phist, pdepths, dReachWords)));
-        }, Flag{wide});
-      }
-      uint32_t flag[GS_REACH_BATCH + 1];
-      HIPCHECK(hipMemcpyAsync(flag, dReachFlag, sizeof flag, hipMemcpyDeviceToHost, stream));
-      HIPCHECK(hipStreamSynchronize(stream));
-      for (int i = 0; i < n; ++i) ran += flag[i] != 0u;
-      ended = flag[n] == 0u;
-    }
+    GS_TRY(runBatched(GS_REACH_BATCH, v.flag, N, "mesh reach: levels did not end after ", "",
+                      [&](int i, int64_t before) {
+                        // (a launch past the search's end returns at once: its level is not used)
+                        const int level = (int)before + i + 1;
+                        with_consts([&](auto w) {
+                          TIMED(this, kReachMembers + GS_REACH_K_LEVEL,
+                                (k_reach_level<CV(w)><<<v.grid, GS_MESH_BLOCK, 0, stream>>>(
+                                    d, v.mask, v.R[(level - 1) & 1], v.R[level & 1], full, level, v.flag + i, prow,
+                                    phist, pdepths, v.words)));
+                        }, Flag{wide});
+                      }, &ran));
     TIMED(this, kReachMembers + GS_REACH_K_FINISH,
-          (k_reach_finish<<<nblk((int64_t)ns * T, 256), 256, 0, stream>>>(d, dReachMask, dReachSrc + k0, ns,
-                                                                           dReachMembers, prow)));
+          (k_reach_finish<<<nblk((int64_t)ns * T, 256), 256, 0, stream>>>(d, v.mask, v.src + k0, ns, v.members, prow)));
     levels += ran;
   }
   HIPCHECK(hipGetLastError());
   unsigned long long words[GS_REACH_W_NUM];
-  HIPCHECK(hipMemcpyAsync(words, dReachWords, sizeof words, hipMemcpyDeviceToHost, stream));
+  HIPCHECK(hipMemcpyAsync(words, v.words, sizeof words, hipMemcpyDeviceToHost, stream));
   HIPCHECK(hipStreamSynchronize(stream));
-  reachPasses += passes;
-  reachLevels += levels;
-  reachBytes += (int64_t)N * 10                                   // members: the subscription word, router and include bytes
-                + (reachDepths ? (int64_t)K * nt : 0)             // the depth table's fill
-                + passes * nt * 8 + (int64_t)K * T * (4 + 8)      // a pass's cleared table, its sources' words
-                + levels * (nt * 16 + (int64_t)N * (10 + 8))      // a level: both tables, the member test, the CSR row bounds
-                + (int64_t)words[GS_REACH_W_GATHER] * 8           // the neighbours' words gathered
-                + (int64_t)words[GS_REACH_W_EDGES] * (8 + 8 + 4 + 4)  // per edge walked: mesh and fanout of the reverse edge, it, the peer
-                + (int64_t)words[GS_REACH_W_DEPTHS]               // depth bytes stored
-                + (int64_t)K * T * (GS_REACH_ROW_T + 1) * 8;      // the row: cleared, UNREACHED
-  reachTaken++;
+  reach.passes += passes;
+  reach.levels += levels;
+  reach.bytes += (int64_t)N * 10                                   // members: the subscription word, router and include bytes
+                 + (reach.depths ? (int64_t)K * nt : 0)            // the depth table's fill
+                 + passes * nt * 8 + (int64_t)K * T * (4 + 8)      // a pass's cleared table, its sources' words
+                 + levels * (nt * 16 + (int64_t)N * (10 + 8))      // a level: both tables, the member test, the CSR row bounds
+                 + (int64_t)words[GS_REACH_W_GATHER] * 8           // the neighbours' words gathered
+                 + (int64_t)words[GS_REACH_W_EDGES] * (8 + 8 + 4 + 4)  // per edge walked: mesh and fanout of the reverse edge, it, the peer
+                 + (int64_t)words[GS_REACH_W_DEPTHS]               // depth bytes stored
+                 + (int64_t)K * T * (GS_REACH_ROW_T + 1) * 8;      // the row: cleared, UNREACHED
   return GS_OK;
 }
 
@@ -1346,7 +1301,7 @@ int gs_engine::stepOne() {
   if (hp.h == 0 && gossip && nOwn()) TIMED(this, GS_K_JOIN, (k_join<<<nOwn(), 64, 0, stream>>>(d, hp.h, hp.now, hp.cur)));
   if (gossip && !floodPublish && hp.n > 0) GS_TRY(fanoutPublish(hp));
   GS_TRY(phaseA(hp));
-  if (latOn) GS_TRY(latencyStats(hp));
+  if (lat.on) GS_TRY(latencyStats(hp));
   GS_TRY(retireAndPublish(hp));
   // the copies the owned senders send next hop, per edge (phase A reads them)
   if (d.pushOvf) HIPCHECK(hipMemsetAsync(d.pushOvf, 0, 4, stream));
@@ -1365,10 +1320,11 @@ int gs_engine::stepOne() {
   HIPCHECK(hipGetLastError());
   if (world > 1) GS_TRY(exchange(hp.cur, heartbeatDue(hp.now)));
   hop++;
-  if (inspOn && hop % inspPeriod == 0) GS_TRY(inspectTick());
-  if (meshOn && hop % meshPeriod == 0) GS_TRY(meshTick());
-  if (reachOn && hop % reachPeriod == 0) GS_TRY(reachTick());
-  if (bwOn && hop % bwPeriod == 0) GS_TRY(bandwidthTick());
+  for (const Tick& t : tickers)
+    if (t.tk->due(hop)) {
+      GS_TRY((this->*t.take)());
+      t.tk->taken++;
+    }
   return GS_OK;
 }
 
@@ -1517,13 +1473,13 @@ int gs_engine::latencyStats(const Hop& hp) {
   const bool inFlight = (hp.amR.m[0] | hp.amR.m[1] | hp.amR.m[2] | hp.amR.m[3]) != 0;
   if (nOwn() && inFlight) {
     const int perBlock = denseFlood ? GS_LAT_BLOCK / 64 : GS_LAT_BLOCK / GS_LAT_GROUP;  // nodes in one pass
-    const unsigned grid = std::min(latGrid, nblk(nOwn(), perBlock));
+    const unsigned grid = std::min(lat.dev.grid, nblk(nOwn(), perBlock));
     TIMED(this, kLatCount, with_consts([&](auto bitmap) {
             k_lat_count<CV(bitmap)><<<grid, GS_LAT_BLOCK, (size_t)S * 4, stream>>>(d, hp.cur, hp.amR);
           }, Flag{denseFlood}));
-    TIMED(this, kLatFold, (k_lat_fold<<<nblk(S, 256), 256, 0, stream>>>(d, hp.h, bins, dLatM, dLatH)));
+    TIMED(this, kLatFold, (k_lat_fold<<<nblk(S, 256), 256, 0, stream>>>(d, hp.h, bins, lat.dev.perMsg, lat.dev.hist)));
   }
-  if (hp.n > 0) k_lat_clear<<<hp.n, 64, 0, stream>>>(d, (int)hp.b, bins, dLatM);
+  if (hp.n > 0) k_lat_clear<<<hp.n, 64, 0, stream>>>(d, (int)hp.b, bins, lat.dev.perMsg);
   return GS_OK;
 }
 
@@ -2411,9 +2367,12 @@ int gs_set_topic_score_params(gs_engine* g, int32_t topic, const gs_topic_score_
 int gs_set_partition(gs_engine* g, int32_t rank, int32_t world, const gs_transport* tr) {
   if (g->started) { gs_set_error("the partition must be set before the first step"); return GS_ESTATE; }
   if (world < 1 || world > 255 || rank < 0 || rank >= world) { gs_set_error("bad rank / world"); return GS_EINVAL; }
-  if (world > 1 && g->meshOn) { gs_set_error("mesh health: not on a partitioned engine"); return GS_EUNSUPPORTED; }
-  if (world > 1 && g->bwOn) { gs_set_error("bandwidth statistics: not on a partitioned engine"); return GS_EUNSUPPORTED; }
-  if (world > 1 && g->reachOn) { gs_set_error("mesh reach: not on a partitioned engine"); return GS_EUNSUPPORTED; }
+  // (bandwidth before mesh reach: the order these refusals have always been tried in)
+  for (const Ticker* tk : {&g->insp.tk, &g->mesh.tk, &g->bw.tk, &g->reach.tk})
+    if (world > 1 && tk->on && tk->oneRank) {
+      gs_set_error(std::string(tk->what) + ": not on a partitioned engine");
+      return GS_EUNSUPPORTED;
+    }
   if (world > 1 && (!tr || !tr->allgather_i64 || !tr->allgather || !tr->alltoallv)) {
     gs_set_error("a partitioned engine needs a transport with allgather_i64, allgather and alltoallv");
     return GS_EINVAL;
@@ -2763,12 +2722,26 @@ int gs_read_deliveries(gs_engine* g, int64_t id, int32_t* hop, int32_t* from) {
 // ---- latency statistics (include/gs_latency.h)
 int gs_set_latency_stats(gs_engine* g, int32_t on) {
   if (g->started) { gs_set_error("latency statistics must be set before the first step"); return GS_ESTATE; }
-  g->latOn = on != 0;
+  g->lat.on = on != 0;
+  return GS_OK;
+}
+
+// The time and launches of the n kernel ids from `first` since the last
+// gs_set_profiling, what is pending on a started engine's stream included.
+static int readKernelStats(gs_engine* g, int first, int n, double* total_ms, int64_t* launches) {
+  if (g->started) {
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    g->resolveTimings();
+  }
+  for (int i = 0; i < n; ++i) {
+    total_ms[i] = g->kMs[first + i];
+    launches[i] = g->kLaunches[first + i];
+  }
   return GS_OK;
 }
 
 static int latency_ready(const gs_engine* g) {
-  if (!g->latOn) { gs_set_error("latency statistics are off (gs_set_latency_stats)"); return GS_ESTATE; }
+  if (!g->lat.on) { gs_set_error("latency statistics are off (gs_set_latency_stats)"); return GS_ESTATE; }
   if (!g->started) { gs_set_error("latency statistics: the engine has not started"); return GS_ESTATE; }
   return GS_OK;
 }
@@ -2789,14 +2762,14 @@ static int latency_bins_ok(const gs_engine* g, int32_t bins) {
 
 int gs_read_latency_hist(gs_engine* g, int64_t* hist, int32_t bins) {
   GS_TRY(latency_bins_ok(g, bins));
-  HIPCHECK(hipMemcpyAsync(hist, g->dLatH, (size_t)g->T * bins * 8, hipMemcpyDeviceToHost, g->stream));
+  HIPCHECK(hipMemcpyAsync(hist, g->lat.dev.hist, (size_t)g->T * bins * 8, hipMemcpyDeviceToHost, g->stream));
   HIPCHECK(hipStreamSynchronize(g->stream));
   return GS_OK;
 }
 
 int gs_reset_latency_stats(gs_engine* g) {
   GS_TRY(latency_ready(g));
-  HIPCHECK(hipMemsetAsync(g->dLatH, 0, (size_t)g->T * g->latBins() * 8, g->stream));
+  HIPCHECK(hipMemsetAsync(g->lat.dev.hist, 0, (size_t)g->T * g->latBins() * 8, g->stream));
   return GS_OK;
 }
 
@@ -2814,7 +2787,7 @@ int gs_read_message_latency(gs_engine* g, int64_t n, const int64_t* ids, uint32_
     if (g->mHop[ids[i]] >= g->hop)  // not yet published: its slot may still hold the earlier owner's row
       std::fill(row, row + bins, 0u);
     else
-      HIPCHECK(hipMemcpyAsync(row, g->dLatM + (size_t)g->mSlot[ids[i]] * bins, (size_t)bins * 4,
+      HIPCHECK(hipMemcpyAsync(row, g->lat.dev.perMsg + (size_t)g->mSlot[ids[i]] * bins, (size_t)bins * 4,
                               hipMemcpyDeviceToHost, g->stream));
   }
   HIPCHECK(hipStreamSynchronize(g->stream));
@@ -2823,23 +2796,12 @@ int gs_read_message_latency(gs_engine* g, int64_t n, const int64_t* ids, uint32_
 
 int gs_read_latency_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
   GS_TRY(latency_ready(g));
-  HIPCHECK(hipStreamSynchronize(g->stream));
-  g->resolveTimings();
-  for (int i = 0; i < 2; ++i) {
-    total_ms[i] = g->kMs[gs_engine::kLatCount + i];
-    launches[i] = g->kLaunches[gs_engine::kLatCount + i];
-  }
-  return GS_OK;
+  return readKernelStats(g, gs_engine::kLatCount, gs_engine::kLatEnd - gs_engine::kLatCount, total_ms, launches);
 }
 
 // ---- WithPeerScoreInspect (include/gs_inspect.h)
 int gs_set_score_inspect(gs_engine* g, const gs_inspect_config* c) {
-  if (g->started) { gs_set_error("the peer score inspector must be set before the first step"); return GS_ESTATE; }
-  if (g->inspOn) { gs_set_error("duplicate peer score inspector"); return GS_ESTATE; }
-  if (g->cfg.router != GS_ROUTER_GOSSIPSUB) { gs_set_error("pubsub router is not gossipsub"); return GS_EUNSUPPORTED; }
-  if (!g->scoring) { gs_set_error("peer scoring is not enabled"); return GS_EUNSUPPORTED; }
-  if (!c || c->period_hops <= 0) { gs_set_error("score inspection: period_hops must be positive"); return GS_EINVAL; }
-  if (c->ticks < 1) { gs_set_error("score inspection: ticks must be at least 1"); return GS_EINVAL; }
+  GS_TRY(g->insp.tk.configure(g, c, Ticker::kGossipsub | Ticker::kScoring));
   if (c->num_bounds < 0 || c->num_bounds > GS_INSPECT_MAX_BOUNDS || (c->num_bounds > 0 && !c->bounds)) {
     gs_set_error("score inspection: num_bounds must be 0.." + std::to_string(GS_INSPECT_MAX_BOUNDS));
     return GS_EINVAL;
@@ -2849,46 +2811,20 @@ int gs_set_score_inspect(gs_engine* g, const gs_inspect_config* c) {
       gs_set_error("score inspection: bounds must be finite and strictly ascending");
       return GS_EINVAL;
     }
-  g->inspPeriod = c->period_hops;
-  g->inspCap = c->ticks;
-  g->inspBounds.assign(c->bounds, c->bounds + c->num_bounds);
-  g->inspMask.clear();
-  if (c->node_mask) g->inspMask.assign(c->node_mask, c->node_mask + g->N);
-  g->inspExt = c->extended != 0;
-  g->inspOn = true;
+  g->insp.bounds.assign(c->bounds, c->bounds + c->num_bounds);
+  g->insp.mask.clear();
+  if (c->node_mask) g->insp.mask.assign(c->node_mask, c->node_mask + g->N);
+  g->insp.ext = c->extended != 0;
+  g->insp.tk.arm(c);
   return GS_OK;
 }
 
-static int inspect_on(const gs_engine* g) {
-  if (!g->inspOn) { gs_set_error("score inspection is off (gs_set_score_inspect)"); return GS_ESTATE; }
-  return GS_OK;
-}
-
-// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
-static int inspect_tick_ok(const gs_engine* g, int64_t tick) {
-  GS_TRY(inspect_on(g));
-  if (tick < 0 || tick >= g->inspTaken) {
-    gs_set_error("score inspection: tick " + std::to_string(tick) + " not taken yet (" +
-                 std::to_string(g->inspTaken) + " so far)");
-    return GS_EINVAL;
-  }
-  if (tick < g->inspTaken - g->inspCap) {
-    gs_set_error("score inspection: tick " + std::to_string(tick) + " already overwritten (ring of " +
-                 std::to_string(g->inspCap) + ")");
-    return GS_ESTATE;
-  }
-  return GS_OK;
-}
-
-int64_t gs_inspect_ticks(const gs_engine* g) {
-  GS_TRY(inspect_on(g));
-  return g->inspTaken;
-}
+int64_t gs_inspect_ticks(const gs_engine* g) { return g->insp.tk.ticksTaken(); }
 
 int gs_inspect_num_edges(const gs_engine* g, int64_t* n) {
-  GS_TRY(inspect_on(g));
+  GS_TRY(g->insp.tk.on_check());
   if (!g->started) { gs_set_error("score inspection: the engine has not started"); return GS_ESTATE; }
-  *n = (int64_t)g->inspEdges.size();
+  *n = (int64_t)g->insp.dev.edges.size();
   return GS_OK;
 }
 
@@ -2896,15 +2832,16 @@ int gs_inspect_edges(gs_engine* g, int64_t* edges, int64_t cap) {
   int64_t n = 0;
   GS_TRY(gs_inspect_num_edges(g, &n));
   if (cap < n || (n > 0 && !edges)) { gs_set_error("score inspection: edge buffer too small"); return GS_EINVAL; }
-  std::copy(g->inspEdges.begin(), g->inspEdges.end(), edges);
+  std::copy(g->insp.dev.edges.begin(), g->insp.dev.edges.end(), edges);
   return GS_OK;
 }
 
 int gs_read_inspect_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* score_hist, int64_t* mesh_deg) {
-  GS_TRY(inspect_tick_ok(g, tick));
-  if (hop) *hop = (tick + 1) * g->inspPeriod;
-  const size_t nh = g->inspBounds.size() + 1;
-  const unsigned long long* row = g->dInspRows + (size_t)(tick % g->inspCap) * g->inspRowLen();
+  const Ticker& tk = g->insp.tk;
+  GS_TRY(tk.tickOk(tick));
+  if (hop) *hop = tk.hopOf(tick);
+  const size_t nh = g->insp.bounds.size() + 1;
+  const unsigned long long* row = g->insp.dev.rows + tk.slotOf(tick) * g->inspRowLen();
   if (score_hist) HIPCHECK(hipMemcpyAsync(score_hist, row, nh * 8, hipMemcpyDeviceToHost, g->stream));
   if (mesh_deg)
     HIPCHECK(hipMemcpyAsync(mesh_deg, row + nh, (size_t)g->T * GS_INSPECT_DEG_BINS * 8, hipMemcpyDeviceToHost,
@@ -2914,10 +2851,10 @@ int gs_read_inspect_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* score
 }
 
 int gs_read_inspect_scores(gs_engine* g, int64_t tick, double* score) {
-  GS_TRY(inspect_tick_ok(g, tick));
-  const size_t nS = g->inspEdges.size();
+  GS_TRY(g->insp.tk.tickOk(tick));
+  const size_t nS = g->insp.dev.edges.size();
   if (nS)
-    HIPCHECK(hipMemcpyAsync(score, g->dInspScore + (size_t)(tick % g->inspCap) * nS, nS * 8, hipMemcpyDeviceToHost,
+    HIPCHECK(hipMemcpyAsync(score, g->insp.dev.score + g->insp.tk.slotOf(tick) * nS, nS * 8, hipMemcpyDeviceToHost,
                             g->stream));
   HIPCHECK(hipStreamSynchronize(g->stream));
   return GS_OK;
@@ -2926,11 +2863,11 @@ int gs_read_inspect_scores(gs_engine* g, int64_t tick, double* score) {
 int gs_read_inspect_snapshot(gs_engine* g, int64_t tick, double* app, double* ip_colocation,
                              double* behaviour_penalty, int64_t* time_in_mesh, double* fmd, double* mmd,
                              double* imd) {
-  GS_TRY(inspect_tick_ok(g, tick));
-  if (!g->inspExt) { gs_set_error("score inspection: the snapshot fields are not kept (extended = 0)"); return GS_ESTATE; }
-  const size_t nS = g->inspEdges.size(), nk = nS * (size_t)g->T;
+  GS_TRY(g->insp.tk.tickOk(tick));
+  if (!g->insp.ext) { gs_set_error("score inspection: the snapshot fields are not kept (extended = 0)"); return GS_ESTATE; }
+  const size_t nS = g->insp.dev.edges.size(), nk = nS * (size_t)g->T;
   if (nS) {
-    const double* x = g->dInspExt + (size_t)(tick % g->inspCap) * g->inspExtLen();
+    const double* x = g->insp.dev.ext + g->insp.tk.slotOf(tick) * g->inspExtLen();
     void* const dst[7] = {app, ip_colocation, behaviour_penalty, time_in_mesh, fmd, mmd, imd};
     size_t off = 0;
     for (int f = 0; f < 7; ++f) {
@@ -2944,61 +2881,28 @@ int gs_read_inspect_snapshot(gs_engine* g, int64_t tick, double* app, double* ip
 }
 
 int gs_read_inspect_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
-  GS_TRY(inspect_on(g));
-  if (g->started) {
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->resolveTimings();
-  }
-  for (int i = 0; i < 3; ++i) {
-    total_ms[i] = g->kMs[gs_engine::kInspScore + i];
-    launches[i] = g->kLaunches[gs_engine::kInspScore + i];
-  }
-  return GS_OK;
+  GS_TRY(g->insp.tk.on_check());
+  return readKernelStats(g, gs_engine::kInspScore, gs_engine::kInspEnd - gs_engine::kInspScore, total_ms, launches);
 }
 
 // ---- mesh health (include/gs_mesh_health.h)
 int gs_set_mesh_health(gs_engine* g, const gs_mesh_health_config* c) {
-  if (g->started) { gs_set_error("the mesh health inspector must be set before the first step"); return GS_ESTATE; }
-  if (g->meshOn) { gs_set_error("duplicate mesh health inspector"); return GS_ESTATE; }
-  if (g->cfg.router != GS_ROUTER_GOSSIPSUB) { gs_set_error("pubsub router is not gossipsub"); return GS_EUNSUPPORTED; }
-  if (g->world > 1) { gs_set_error("mesh health: not on a partitioned engine"); return GS_EUNSUPPORTED; }
-  if (!c || c->period_hops <= 0) { gs_set_error("mesh health: period_hops must be positive"); return GS_EINVAL; }
-  if (c->ticks < 1) { gs_set_error("mesh health: ticks must be at least 1"); return GS_EINVAL; }
-  g->meshPeriod = c->period_hops;
-  g->meshCap = c->ticks;
-  g->meshMask.clear();
-  if (c->include) g->meshMask.assign(c->include, c->include + g->N);
-  g->meshLabels = c->labels != 0;
-  g->meshOn = true;
+  GS_TRY(g->mesh.tk.configure(g, c, Ticker::kGossipsub));
+  g->mesh.mask.clear();
+  if (c->include) g->mesh.mask.assign(c->include, c->include + g->N);
+  g->mesh.labels = c->labels != 0;
+  g->mesh.tk.arm(c);
   return GS_OK;
 }
 
-static int mesh_on(const gs_engine* g) {
-  if (!g->meshOn) { gs_set_error("mesh health is off (gs_set_mesh_health)"); return GS_ESTATE; }
-  return GS_OK;
-}
+int64_t gs_mesh_health_ticks(const gs_engine* g) { return g->mesh.tk.ticksTaken(); }
 
-int64_t gs_mesh_health_ticks(const gs_engine* g) {
-  GS_TRY(mesh_on(g));
-  return g->meshTaken;
-}
-
-// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
 int gs_read_mesh_health_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* row, int64_t* comp_hist) {
-  GS_TRY(mesh_on(g));
-  if (tick < 0 || tick >= g->meshTaken) {
-    gs_set_error("mesh health: tick " + std::to_string(tick) + " not taken yet (" + std::to_string(g->meshTaken) +
-                 " so far)");
-    return GS_EINVAL;
-  }
-  if (tick < g->meshTaken - g->meshCap) {
-    gs_set_error("mesh health: tick " + std::to_string(tick) + " already overwritten (ring of " +
-                 std::to_string(g->meshCap) + ")");
-    return GS_ESTATE;
-  }
-  if (hop) *hop = (tick + 1) * g->meshPeriod;
+  const Ticker& tk = g->mesh.tk;
+  GS_TRY(tk.tickOk(tick));
+  if (hop) *hop = tk.hopOf(tick);
   const size_t nf = (size_t)g->T * GS_MESH_ROW_FIELDS;
-  const unsigned long long* src = g->dMeshRows + (size_t)(tick % g->meshCap) * (size_t)mesh_row_len(g->T);
+  const unsigned long long* src = g->mesh.dev.rows + tk.slotOf(tick) * (size_t)mesh_row_len(g->T);
   if (row) HIPCHECK(hipMemcpyAsync(row, src, nf * 8, hipMemcpyDeviceToHost, g->stream));
   if (comp_hist)
     HIPCHECK(hipMemcpyAsync(comp_hist, src + nf, (size_t)g->T * GS_MESH_SIZE_BINS * 8, hipMemcpyDeviceToHost,
@@ -3009,40 +2913,28 @@ int gs_read_mesh_health_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* r
 
 // The label table is the newest tick's until the next tick starts over.
 int gs_read_mesh_labels(gs_engine* g, int64_t* tick, int32_t* labels) {
-  GS_TRY(mesh_on(g));
-  if (!g->meshLabels) { gs_set_error("mesh health: the label table is not kept (labels = 0)"); return GS_ESTATE; }
-  if (g->meshTaken == 0) { gs_set_error("mesh health: no tick taken yet"); return GS_EINVAL; }
-  if (tick) *tick = g->meshTaken - 1;
+  GS_TRY(g->mesh.tk.on_check());
+  if (!g->mesh.labels) { gs_set_error("mesh health: the label table is not kept (labels = 0)"); return GS_ESTATE; }
+  if (g->mesh.tk.taken == 0) { gs_set_error("mesh health: no tick taken yet"); return GS_EINVAL; }
+  if (tick) *tick = g->mesh.tk.taken - 1;
   if (labels)  // GS_MESH_NONE reads -1
-    HIPCHECK(hipMemcpyAsync(labels, g->dMeshL, (size_t)g->N * (size_t)g->T * 4, hipMemcpyDeviceToHost, g->stream));
+    HIPCHECK(hipMemcpyAsync(labels, g->mesh.dev.L, (size_t)g->N * (size_t)g->T * 4, hipMemcpyDeviceToHost, g->stream));
   HIPCHECK(hipStreamSynchronize(g->stream));
   return GS_OK;
 }
 
 int gs_read_mesh_health_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
-  GS_TRY(mesh_on(g));
-  if (g->started) {
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->resolveTimings();
-  }
-  for (int i = 0; i < GS_MESH_ST_ITERS; ++i) {
-    total_ms[i] = g->kMs[gs_engine::kMeshInit + i];
-    launches[i] = g->kLaunches[gs_engine::kMeshInit + i];
-  }
+  GS_TRY(g->mesh.tk.on_check());
+  GS_TRY(readKernelStats(g, gs_engine::kMeshInit, GS_MESH_ST_ITERS, total_ms, launches));
   total_ms[GS_MESH_ST_ITERS] = total_ms[GS_MESH_ST_BYTES] = 0.0;
-  launches[GS_MESH_ST_ITERS] = g->meshIters;
-  launches[GS_MESH_ST_BYTES] = g->meshBytes;
+  launches[GS_MESH_ST_ITERS] = g->mesh.iters;
+  launches[GS_MESH_ST_BYTES] = g->mesh.bytes;
   return GS_OK;
 }
 
 // ---- bandwidth statistics (include/gs_bandwidth.h)
 int gs_set_bandwidth_stats(gs_engine* g, const gs_bandwidth_config* c) {
-  if (g->started) { gs_set_error("the bandwidth statistics must be set before the first step"); return GS_ESTATE; }
-  if (g->bwOn) { gs_set_error("duplicate bandwidth statistics"); return GS_ESTATE; }
-  if (!g->acctOn) { gs_set_error("bandwidth statistics: RPC accounting is off"); return GS_ESTATE; }
-  if (g->world > 1) { gs_set_error("bandwidth statistics: not on a partitioned engine"); return GS_EUNSUPPORTED; }
-  if (!c || c->period_hops <= 0) { gs_set_error("bandwidth statistics: period_hops must be positive"); return GS_EINVAL; }
-  if (c->ticks < 1) { gs_set_error("bandwidth statistics: ticks must be at least 1"); return GS_EINVAL; }
+  GS_TRY(g->bw.tk.configure(g, c, Ticker::kAccounting));
   if (c->num_bounds < 0 || c->num_bounds > GS_BW_MAX_BOUNDS || (c->num_bounds > 0 && !c->bounds)) {
     gs_set_error("bandwidth statistics: num_bounds must be 0.." + std::to_string(GS_BW_MAX_BOUNDS));
     return GS_EINVAL;
@@ -3052,46 +2944,20 @@ int gs_set_bandwidth_stats(gs_engine* g, const gs_bandwidth_config* c) {
       gs_set_error("bandwidth statistics: bounds must be positive and strictly ascending");
       return GS_EINVAL;
     }
-  g->bwPeriod = c->period_hops;
-  g->bwCap = c->ticks;
-  g->bwBounds.assign(c->bounds, c->bounds + c->num_bounds);
-  g->bwNodes.clear();
+  g->bw.bounds.assign(c->bounds, c->bounds + c->num_bounds);
+  g->bw.nodes.clear();
   if (c->node_mask)
     for (int u = 0; u < g->N; ++u)
-      if (c->node_mask[u]) g->bwNodes.push_back(u);
-  g->bwOn = true;
+      if (c->node_mask[u]) g->bw.nodes.push_back(u);
+  g->bw.tk.arm(c);
   return GS_OK;
 }
 
-static int bandwidth_on(const gs_engine* g) {
-  if (!g->bwOn) { gs_set_error("the bandwidth statistics are off (gs_set_bandwidth_stats)"); return GS_ESTATE; }
-  return GS_OK;
-}
-
-// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
-static int bandwidth_tick_ok(const gs_engine* g, int64_t tick) {
-  GS_TRY(bandwidth_on(g));
-  if (tick < 0 || tick >= g->bwTaken) {
-    gs_set_error("bandwidth statistics: tick " + std::to_string(tick) + " not taken yet (" +
-                 std::to_string(g->bwTaken) + " so far)");
-    return GS_EINVAL;
-  }
-  if (tick < g->bwTaken - g->bwCap) {
-    gs_set_error("bandwidth statistics: tick " + std::to_string(tick) + " already overwritten (ring of " +
-                 std::to_string(g->bwCap) + ")");
-    return GS_ESTATE;
-  }
-  return GS_OK;
-}
-
-int64_t gs_bandwidth_ticks(const gs_engine* g) {
-  GS_TRY(bandwidth_on(g));
-  return g->bwTaken;
-}
+int64_t gs_bandwidth_ticks(const gs_engine* g) { return g->bw.tk.ticksTaken(); }
 
 int gs_bandwidth_num_nodes(const gs_engine* g, int64_t* n) {
-  GS_TRY(bandwidth_on(g));
-  *n = (int64_t)g->bwNodes.size();
+  GS_TRY(g->bw.tk.on_check());
+  *n = (int64_t)g->bw.nodes.size();
   return GS_OK;
 }
 
@@ -3099,15 +2965,16 @@ int gs_bandwidth_nodes(gs_engine* g, int32_t* nodes, int64_t cap) {
   int64_t n = 0;
   GS_TRY(gs_bandwidth_num_nodes(g, &n));
   if (cap < n || (n > 0 && !nodes)) { gs_set_error("bandwidth statistics: node buffer too small"); return GS_EINVAL; }
-  std::copy(g->bwNodes.begin(), g->bwNodes.end(), nodes);
+  std::copy(g->bw.nodes.begin(), g->bw.nodes.end(), nodes);
   return GS_OK;
 }
 
 int gs_read_bandwidth_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* total, int64_t* total_rpcs,
                           int64_t* hist, int64_t* max, int64_t* argmax) {
-  GS_TRY(bandwidth_tick_ok(g, tick));
-  if (hop) *hop = (tick + 1) * g->bwPeriod;
-  const unsigned long long* row = g->dBwRows + (size_t)(tick % g->bwCap) * g->bwRowLen();
+  const Ticker& tk = g->bw.tk;
+  GS_TRY(tk.tickOk(tick));
+  if (hop) *hop = tk.hopOf(tick);
+  const unsigned long long* row = g->bw.dev.rows + tk.slotOf(tick) * g->bwRowLen();
   const size_t nw = (size_t)GS_BW_DIRS * GS_BW_CLASSES;
   const auto get = [&](int64_t* dst, size_t at, size_t n) {
     return dst ? hipMemcpyAsync(dst, row + at, n * 8, hipMemcpyDeviceToHost, g->stream) : hipSuccess;
@@ -3116,45 +2983,32 @@ int gs_read_bandwidth_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* tot
   HIPCHECK(get(total_rpcs, GS_BW_CLASSES, 1));
   HIPCHECK(get(max, GS_BW_ROW_MAX, nw));
   HIPCHECK(get(argmax, GS_BW_ROW_ARG, nw));
-  HIPCHECK(get(hist, GS_BW_ROW_HIST, nw * (g->bwBounds.size() + 1)));
+  HIPCHECK(get(hist, GS_BW_ROW_HIST, nw * (g->bw.bounds.size() + 1)));
   HIPCHECK(hipStreamSynchronize(g->stream));
   return GS_OK;
 }
 
 int gs_read_bandwidth_nodes(gs_engine* g, int64_t tick, int64_t* bytes, int64_t* rpcs) {
-  GS_TRY(bandwidth_tick_ok(g, tick));
-  const size_t nS = g->bwNodes.size(), slot = (size_t)(tick % g->bwCap);
+  GS_TRY(g->bw.tk.tickOk(tick));
+  const size_t nS = g->bw.nodes.size(), slot = g->bw.tk.slotOf(tick);
   if (nS && bytes)
-    HIPCHECK(hipMemcpyAsync(bytes, g->dBwBytes + slot * nS * GS_BW_NODE_WORDS, nS * GS_BW_NODE_WORDS * 8,
+    HIPCHECK(hipMemcpyAsync(bytes, g->bw.dev.bytes + slot * nS * GS_BW_NODE_WORDS, nS * GS_BW_NODE_WORDS * 8,
                             hipMemcpyDeviceToHost, g->stream));
   if (nS && rpcs)
-    HIPCHECK(hipMemcpyAsync(rpcs, g->dBwRpcs + slot * nS * GS_BW_DIRS, nS * GS_BW_DIRS * 8, hipMemcpyDeviceToHost,
+    HIPCHECK(hipMemcpyAsync(rpcs, g->bw.dev.rpcs + slot * nS * GS_BW_DIRS, nS * GS_BW_DIRS * 8, hipMemcpyDeviceToHost,
                             g->stream));
   HIPCHECK(hipStreamSynchronize(g->stream));
   return GS_OK;
 }
 
 int gs_read_bandwidth_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
-  GS_TRY(bandwidth_on(g));
-  if (g->started) {
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->resolveTimings();
-  }
-  for (int i = 0; i < GS_BW_NUM_STATS; ++i) {
-    total_ms[i] = g->kMs[gs_engine::kBwTick + i];
-    launches[i] = g->kLaunches[gs_engine::kBwTick + i];
-  }
-  return GS_OK;
+  GS_TRY(g->bw.tk.on_check());
+  return readKernelStats(g, gs_engine::kBwTick, GS_BW_NUM_STATS, total_ms, launches);
 }
 
 // ---- mesh reach (include/gs_mesh_reach.h)
 int gs_set_mesh_reach(gs_engine* g, const gs_mesh_reach_config* c) {
-  if (g->started) { gs_set_error("the mesh reach inspector must be set before the first step"); return GS_ESTATE; }
-  if (g->reachOn) { gs_set_error("duplicate mesh reach inspector"); return GS_ESTATE; }
-  if (g->cfg.router != GS_ROUTER_GOSSIPSUB) { gs_set_error("pubsub router is not gossipsub"); return GS_EUNSUPPORTED; }
-  if (g->world > 1) { gs_set_error("mesh reach: not on a partitioned engine"); return GS_EUNSUPPORTED; }
-  if (!c || c->period_hops <= 0) { gs_set_error("mesh reach: period_hops must be positive"); return GS_EINVAL; }
-  if (c->ticks < 1) { gs_set_error("mesh reach: ticks must be at least 1"); return GS_EINVAL; }
+  GS_TRY(g->reach.tk.configure(g, c, Ticker::kGossipsub));
   if (c->num_sources < 1 || c->num_sources > GS_REACH_MAX_SOURCES) {
     gs_set_error("mesh reach: num_sources must be 1 .. " + std::to_string(GS_REACH_MAX_SOURCES));
     return GS_EINVAL;
@@ -3171,43 +3025,23 @@ int gs_set_mesh_reach(gs_engine* g, const gs_mesh_reach_config* c) {
     gs_set_error("mesh reach: source " + std::to_string(*dup) + " is given twice");
     return GS_EINVAL;
   }
-  g->reachPeriod = c->period_hops;
-  g->reachCap = c->ticks;
-  g->reachSrc = std::move(src);
-  g->reachMask.clear();
-  if (c->include) g->reachMask.assign(c->include, c->include + g->N);
-  g->reachDepths = c->depths != 0;
-  g->reachOn = true;
+  g->reach.src = std::move(src);
+  g->reach.mask.clear();
+  if (c->include) g->reach.mask.assign(c->include, c->include + g->N);
+  g->reach.depths = c->depths != 0;
+  g->reach.tk.arm(c);
   return GS_OK;
 }
 
-static int reach_on(const gs_engine* g) {
-  if (!g->reachOn) { gs_set_error("mesh reach is off (gs_set_mesh_reach)"); return GS_ESTATE; }
-  return GS_OK;
-}
+int64_t gs_mesh_reach_ticks(const gs_engine* g) { return g->reach.tk.ticksTaken(); }
 
-int64_t gs_mesh_reach_ticks(const gs_engine* g) {
-  GS_TRY(reach_on(g));
-  return g->reachTaken;
-}
-
-// A read of tick k is valid while ticks_taken - capacity <= k < ticks_taken.
 int gs_read_mesh_reach_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* row, int64_t* depth_hist) {
-  GS_TRY(reach_on(g));
-  if (tick < 0 || tick >= g->reachTaken) {
-    gs_set_error("mesh reach: tick " + std::to_string(tick) + " not taken yet (" + std::to_string(g->reachTaken) +
-                 " so far)");
-    return GS_EINVAL;
-  }
-  if (tick < g->reachTaken - g->reachCap) {
-    gs_set_error("mesh reach: tick " + std::to_string(tick) + " already overwritten (ring of " +
-                 std::to_string(g->reachCap) + ")");
-    return GS_ESTATE;
-  }
-  if (hop) *hop = (tick + 1) * g->reachPeriod;
-  const int K = (int)g->reachSrc.size();
+  const Ticker& tk = g->reach.tk;
+  GS_TRY(tk.tickOk(tick));
+  if (hop) *hop = tk.hopOf(tick);
+  const int K = (int)g->reach.src.size();
   const size_t nf = (size_t)K * g->T * GS_REACH_ROW_FIELDS;
-  const unsigned long long* src = g->dReachRows + (size_t)(tick % g->reachCap) * (size_t)reach_row_len(K, g->T);
+  const unsigned long long* src = g->reach.dev.rows + tk.slotOf(tick) * (size_t)reach_row_len(K, g->T);
   if (row) HIPCHECK(hipMemcpyAsync(row, src, nf * 8, hipMemcpyDeviceToHost, g->stream));
   if (depth_hist)
     HIPCHECK(hipMemcpyAsync(depth_hist, src + nf, (size_t)K * g->T * GS_REACH_DEPTH_BINS * 8, hipMemcpyDeviceToHost,
@@ -3218,31 +3052,24 @@ int gs_read_mesh_reach_row(gs_engine* g, int64_t tick, int64_t* hop, int64_t* ro
 
 // The depth table is the newest tick's until the next tick starts over.
 int gs_read_mesh_reach_depths(gs_engine* g, int64_t* tick, uint8_t* depths) {
-  GS_TRY(reach_on(g));
-  if (!g->reachDepths) { gs_set_error("mesh reach: the depth table is not kept (depths = 0)"); return GS_ESTATE; }
-  if (g->reachTaken == 0) { gs_set_error("mesh reach: no tick taken yet"); return GS_EINVAL; }
-  if (tick) *tick = g->reachTaken - 1;
+  GS_TRY(g->reach.tk.on_check());
+  if (!g->reach.depths) { gs_set_error("mesh reach: the depth table is not kept (depths = 0)"); return GS_ESTATE; }
+  if (g->reach.tk.taken == 0) { gs_set_error("mesh reach: no tick taken yet"); return GS_EINVAL; }
+  if (tick) *tick = g->reach.tk.taken - 1;
   if (depths)
-    HIPCHECK(hipMemcpyAsync(depths, g->dReachDepths, g->reachSrc.size() * (size_t)g->N * (size_t)g->T,
+    HIPCHECK(hipMemcpyAsync(depths, g->reach.dev.depths, g->reach.src.size() * (size_t)g->N * (size_t)g->T,
                             hipMemcpyDeviceToHost, g->stream));
   HIPCHECK(hipStreamSynchronize(g->stream));
   return GS_OK;
 }
 
 int gs_read_mesh_reach_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
-  GS_TRY(reach_on(g));
-  if (g->started) {
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->resolveTimings();
-  }
-  for (int i = 0; i < GS_REACH_ST_PASSES; ++i) {
-    total_ms[i] = g->kMs[gs_engine::kReachMembers + i];
-    launches[i] = g->kLaunches[gs_engine::kReachMembers + i];
-  }
+  GS_TRY(g->reach.tk.on_check());
+  GS_TRY(readKernelStats(g, gs_engine::kReachMembers, GS_REACH_ST_PASSES, total_ms, launches));
   total_ms[GS_REACH_ST_PASSES] = total_ms[GS_REACH_ST_LEVELS] = total_ms[GS_REACH_ST_BYTES] = 0.0;
-  launches[GS_REACH_ST_PASSES] = g->reachPasses;
-  launches[GS_REACH_ST_LEVELS] = g->reachLevels;
-  launches[GS_REACH_ST_BYTES] = g->reachBytes;
+  launches[GS_REACH_ST_PASSES] = g->reach.passes;
+  launches[GS_REACH_ST_LEVELS] = g->reach.levels;
+  launches[GS_REACH_ST_BYTES] = g->reach.bytes;
   return GS_OK;
 }
 
@@ -3268,18 +3095,13 @@ int gs_set_profiling(gs_engine* g, int on) {
   }
   g->profiling = on != 0;
   for (int i = 0; i < gs_engine::kTimed; ++i) { g->kMs[i] = 0; g->kLaunches[i] = 0; }
-  g->meshIters = g->meshBytes = 0;
-  g->reachPasses = g->reachLevels = g->reachBytes = 0;
+  g->mesh.iters = g->mesh.bytes = 0;
+  g->reach.passes = g->reach.levels = g->reach.bytes = 0;
   return GS_OK;
 }
 
 int gs_read_kernel_stats(gs_engine* g, double* total_ms, int64_t* launches) {
-  if (g->started) {
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->resolveTimings();
-  }
-  for (int i = 0; i < GS_NUM_KERNELS; ++i) { total_ms[i] = g->kMs[i]; launches[i] = g->kLaunches[i]; }
-  return GS_OK;
+  return readKernelStats(g, 0, GS_NUM_KERNELS, total_ms, launches);
 }
 
 }  // extern "C"

@@ -391,6 +391,29 @@ def WithPartition(rank, world, transport):
     return ("partition", (int(rank), int(world), transport))
 
 
+# The headers only the product library exports (include/gs_window.h, gs_latency.h,
+# gs_inspect.h, gs_mesh_health.h, gs_mesh_reach.h, gs_bandwidth.h): their
+# functions and how Engine._product names them when the library lacks them.
+_PRODUCT_ONLY = {
+    "windows": (_abi.WINDOW_FUNCTIONS, "topic windows (WithTopicWindows)"),
+    "latency": (_abi.LATENCY_FUNCTIONS, "latency statistics (WithLatencyStats)"),
+    "inspect": (_abi.INSPECT_FUNCTIONS, "score inspection (WithPeerScoreInspect)"),
+    "mesh_health": (_abi.MESH_HEALTH_FUNCTIONS, "mesh health (WithMeshHealth)"),
+    "mesh_reach": (_abi.MESH_REACH_FUNCTIONS, "mesh reach (WithMeshReach)"),
+    "bandwidth": (_abi.BANDWIDTH_FUNCTIONS, "bandwidth statistics (WithBandwidthStats)"),
+}
+
+
+def _node_mask(nodes, num_nodes):
+    """uint8 [num_nodes]: 1 at the hosts of `nodes` (indices or a bool mask); None for None."""
+    if nodes is None:
+        return None
+    mask = np.zeros(num_nodes, dtype=np.uint8)
+    nodes = np.asarray(nodes)
+    mask[np.nonzero(nodes)[0] if nodes.dtype == bool else nodes.astype(np.int64)] = 1
+    return mask
+
+
 class Engine:
     """One batched simulation of N routers (see module docstring)."""
 
@@ -461,14 +484,9 @@ class Engine:
             C.byref(thr_c) if thr_c is not None else None,
             C.byref(opts["gater"].to_c()) if opts.get("gater") is not None else None, C.byref(h)))
         self.h = h
-        # include/gs_window.h: exported by the product library only
-        self._has_windows = all(hasattr(self.lib, name) for name, _, _ in _abi.WINDOW_FUNCTIONS)
-        if self._has_windows:
-            for name, res, args in _abi.WINDOW_FUNCTIONS:
-                fn = getattr(self.lib, name)
-                fn.restype, fn.argtypes = res, args
+        self._has = {feature: self._bind(functions) for feature, (functions, _) in _PRODUCT_ONLY.items()}
         tw = opts.get("topic_windows")
-        if tw is not None and self._has_windows:  # (the oracle has no window)
+        if tw is not None and self._has["windows"]:  # (the oracle has no window)
             for a, what in zip(tw, ("slots", "max_age_hops")):
                 if a is not None and len(a) != num_topics:
                     self.close()
@@ -512,63 +530,28 @@ class Engine:
             _check(self.lib, self.lib.gs_set_peertx_capacity(h, *ptx))
         if opts.get("frontier_mode"):
             _check(self.lib, self.lib.gs_set_frontier_mode(h, opts["frontier_mode"]))
-        # include/gs_latency.h: exported by the product library only
-        self._has_latency = all(hasattr(self.lib, name) for name, _, _ in _abi.LATENCY_FUNCTIONS)
-        if self._has_latency:
-            for name, res, args in _abi.LATENCY_FUNCTIONS:
-                fn = getattr(self.lib, name)
-                fn.restype, fn.argtypes = res, args
+        # the product-only options: a library without one's exports closes the engine and raises
         if opts.get("latency_stats"):
-            if not self._has_latency:
-                self.close()
-            _check(self.lib, self._latency_lib().gs_set_latency_stats(h, 1))
-        # include/gs_inspect.h: exported by the product library only
-        self._has_inspect = all(hasattr(self.lib, name) for name, _, _ in _abi.INSPECT_FUNCTIONS)
-        if self._has_inspect:
-            for name, res, args in _abi.INSPECT_FUNCTIONS:
-                fn = getattr(self.lib, name)
-                fn.restype, fn.argtypes = res, args
+            _check(self.lib, self._product("latency", closing=True).gs_set_latency_stats(h, 1))
         self._inspect = None
         if insp is not None:
-            if not self._has_inspect:
-                self.close()
-            lib = self._inspect_lib()
+            lib = self._product("inspect", closing=True)
             bounds = insp["bounds"]
             if bounds is None:
                 bounds = _checked_bounds(default_inspect_bounds(score[1])) if score is not None else np.zeros(0)
-            mask = None
-            if insp["nodes"] is not None:
-                mask = np.zeros(num_nodes, dtype=np.uint8)
-                nodes = np.asarray(insp["nodes"])
-                mask[np.nonzero(nodes)[0] if nodes.dtype == bool else nodes.astype(np.int64)] = 1
+            mask = _node_mask(insp["nodes"], num_nodes)
             ic = _abi.InspectConfigC(insp["period_hops"], insp["ticks"], len(bounds), _ptr(bounds, C.c_double),
                                      _ptr(mask, C.c_uint8), 1 if insp["extended"] else 0)
             _check(lib, lib.gs_set_score_inspect(h, C.byref(ic)))
             self._inspect = dict(insp, bounds=bounds, mask=mask, delivered=0)
-        # include/gs_mesh_health.h: exported by the product library only
-        self._has_mesh_health = all(hasattr(self.lib, name) for name, _, _ in _abi.MESH_HEALTH_FUNCTIONS)
-        if self._has_mesh_health:
-            for name, res, args in _abi.MESH_HEALTH_FUNCTIONS:
-                fn = getattr(self.lib, name)
-                fn.restype, fn.argtypes = res, args
         if mh is not None:
-            if not self._has_mesh_health:
-                self.close()
-            lib = self._mesh_health_lib()
+            lib = self._product("mesh_health", closing=True)
             mask = np.ascontiguousarray(np.asarray(mh["nodes"]) != 0, dtype=np.uint8) if mh["nodes"] is not None else None
             mc = _abi.MeshHealthConfigC(mh["period_hops"], mh["ticks"], _ptr(mask, C.c_uint8), 1 if mh["labels"] else 0)
             _check(lib, lib.gs_set_mesh_health(h, C.byref(mc)))
-        # include/gs_mesh_reach.h: exported by the product library only
-        self._has_mesh_reach = all(hasattr(self.lib, name) for name, _, _ in _abi.MESH_REACH_FUNCTIONS)
-        if self._has_mesh_reach:
-            for name, res, args in _abi.MESH_REACH_FUNCTIONS:
-                fn = getattr(self.lib, name)
-                fn.restype, fn.argtypes = res, args
         self._reach_sources = 0
         if mr is not None:
-            if not self._has_mesh_reach:
-                self.close()
-            lib = self._mesh_reach_lib()
+            lib = self._product("mesh_reach", closing=True)
             mask = np.ascontiguousarray(np.asarray(mr["nodes"]) != 0, dtype=np.uint8) if mr["nodes"] is not None else None
             src = np.ascontiguousarray(mr["sources"], dtype=np.int32)
             rc = _abi.MeshReachConfigC(mr["period_hops"], mr["ticks"], len(src), _ptr(src, C.c_int32),
@@ -584,22 +567,10 @@ class Engine:
             _check(self.lib, self.lib.gs_set_rpc_accounting(h, _ptr(ms, C.c_int32), idl, _ptr(tl, C.c_int32)))
             _check(self.lib, self.lib.gs_set_rpc_px_sizes(h, pid, rec))
         self.rpc_acct = acct is not None
-        # include/gs_bandwidth.h: exported by the product library only; after the accounting it needs
-        self._has_bandwidth = all(hasattr(self.lib, name) for name, _, _ in _abi.BANDWIDTH_FUNCTIONS)
-        if self._has_bandwidth:
-            for name, res, args in _abi.BANDWIDTH_FUNCTIONS:
-                fn = getattr(self.lib, name)
-                fn.restype, fn.argtypes = res, args
         self._bw_bounds = None
-        if bw is not None:
-            if not self._has_bandwidth:
-                self.close()
-            lib = self._bandwidth_lib()
-            mask = None
-            if bw["nodes"] is not None:
-                mask = np.zeros(num_nodes, dtype=np.uint8)
-                nodes = np.asarray(bw["nodes"])
-                mask[np.nonzero(nodes)[0] if nodes.dtype == bool else nodes.astype(np.int64)] = 1
+        if bw is not None:  # after the accounting it needs
+            lib = self._product("bandwidth", closing=True)
+            mask = _node_mask(bw["nodes"], num_nodes)
             bc = _abi.BandwidthConfigC(bw["period_hops"], bw["ticks"], len(bw["bounds"]), _ptr(bw["bounds"], C.c_int64),
                                        _ptr(mask, C.c_uint8))
             _check(lib, lib.gs_set_bandwidth_stats(h, C.byref(bc)))
@@ -651,6 +622,43 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+    # ---------------------------------------------------------------- the product-only headers
+    def _bind(self, functions):
+        """Binds restype / argtypes of a header's `functions` if the library
+        exports them all; whether it does."""
+        if not all(hasattr(self.lib, name) for name, _, _ in functions):
+            return False
+        for name, res, args in functions:
+            fn = getattr(self.lib, name)
+            fn.restype, fn.argtypes = res, args
+        return True
+
+    def _product(self, feature, closing=False):
+        """The library, if it exports the header of `feature` (_PRODUCT_ONLY);
+        else ValueError, from __init__ (`closing`) after closing the engine."""
+        if not self._has[feature]:
+            if closing:
+                self.close()
+            raise ValueError(f"{_PRODUCT_ONLY[feature][1]}: product library only")
+        return self.lib
+
+    def _ticks(self, fn):
+        """Ticks taken so far; a negative result is the call's GS_* code."""
+        n = fn(self.h)
+        if n < 0:
+            _check(self.lib, int(n))
+        return int(n)
+
+    def _kernel_stats(self, fn, names, n, counters=()):
+        """{name: (total_ms, launches)} of the call's first len(names) of n
+        entries, and {counter: launches[]} of the `counters` that follow them."""
+        ms = np.zeros(n, dtype=np.float64)
+        cnt = np.zeros(n, dtype=np.int64)
+        _check(self.lib, fn(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
+        out = {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(names)}
+        out.update((k, int(cnt[len(names) + j])) for j, k in enumerate(counters))
+        return out
 
     # ---------------------------------------------------------------- driving
     def publish(self, src, topic, hop, kind=None):
@@ -825,20 +833,14 @@ class Engine:
         in force per topic (gs_read_topic_windows): its ring, the age up to which
         a first delivery is accepted, and the hops after which its slots are
         taken again.  Product library only."""
-        if not self._has_windows:
-            raise ValueError("topic windows (WithTopicWindows): product library only")
+        lib = self._product("windows")
         out = [np.zeros(self.T, dtype=np.int32) for _ in range(3)]
-        _check(self.lib, self.lib.gs_read_topic_windows(self.h, *[_ptr(a, C.c_int32) for a in out]))
+        _check(lib, lib.gs_read_topic_windows(self.h, *[_ptr(a, C.c_int32) for a in out]))
         return tuple(out)
-
-    def _latency_lib(self):
-        if not self._has_latency:
-            raise ValueError("latency statistics (WithLatencyStats): product library only")
-        return self.lib
 
     def latency_bins(self):
         """maxAge + 1 (gs_latency_bins), once the engine has started."""
-        lib = self._latency_lib()
+        lib = self._product("latency")
         bins = lib.gs_latency_bins(self.h)
         if bins < 0:
             _check(lib, bins)
@@ -865,34 +867,21 @@ class Engine:
 
     def reset_latency_stats(self):
         """Zeroes the per-topic table (message_latency is unaffected)."""
-        _check(self._latency_lib(), self.lib.gs_reset_latency_stats(self.h))
+        _check(self.lib, self._product("latency").gs_reset_latency_stats(self.h))
 
     def latency_kernel_stats(self):
         """{"lat_count" | "lat_fold": (total_ms, launches)} since set_profiling(True)."""
-        ms = np.zeros(2, dtype=np.float64)
-        cnt = np.zeros(2, dtype=np.int64)
-        _check(self._latency_lib(), self.lib.gs_read_latency_kernel_stats(self.h, _ptr(ms, C.c_double),
-                                                                          _ptr(cnt, C.c_int64)))
-        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(("lat_count", "lat_fold"))}
+        return self._kernel_stats(self._product("latency").gs_read_latency_kernel_stats, ("lat_count", "lat_fold"), 2)
 
     # ---------------------------------------------------------------- score inspection
-    def _inspect_lib(self):
-        if not self._has_inspect:
-            raise ValueError("score inspection (WithPeerScoreInspect): product library only")
-        return self.lib
-
     def inspect_ticks(self):
         """Ticks taken so far (gs_inspect_ticks)."""
-        lib = self._inspect_lib()
-        n = lib.gs_inspect_ticks(self.h)
-        if n < 0:
-            _check(lib, int(n))
-        return int(n)
+        return self._ticks(self._product("inspect").gs_inspect_ticks)
 
     def inspect_row(self, k):
         """Tick k: dict(hop, score_hist int64 [len(bounds) + 1], mesh_deg int64
         [T, 65]) of this rank's owned edges and nodes (gs_read_inspect_row)."""
-        lib = self._inspect_lib()
+        lib = self._product("inspect")
         nb = len(self._inspect["bounds"]) if self._inspect else 0
         hop = C.c_int64()
         hist = np.zeros(nb + 1, dtype=np.int64)
@@ -903,7 +892,7 @@ class Engine:
 
     def inspect_edges(self):
         """The sampled edges of this rank (the out-edges of its observers), ascending."""
-        lib = self._inspect_lib()
+        lib = self._product("inspect")
         n = C.c_int64()
         _check(lib, lib.gs_inspect_num_edges(self.h, C.byref(n)))
         edges = np.zeros(n.value, dtype=np.int64)
@@ -912,7 +901,7 @@ class Engine:
 
     def inspect_scores(self, k):
         """The sampled edges' scores at tick k, float64 [len(inspect_edges())]."""
-        lib = self._inspect_lib()
+        lib = self._product("inspect")
         n = C.c_int64()
         _check(lib, lib.gs_inspect_num_edges(self.h, C.byref(n)))
         a = np.zeros(n.value, dtype=np.float64)
@@ -923,7 +912,7 @@ class Engine:
         """The sampled edges' PeerScoreSnapshot fields at tick k (extended=True):
         dict(app, ip_colocation, behaviour_penalty [nS]; time_in_mesh int64, fmd,
         mmd, imd [nS, T])."""
-        lib = self._inspect_lib()
+        lib = self._product("inspect")
         n = C.c_int64()
         _check(lib, lib.gs_inspect_num_edges(self.h, C.byref(n)))
         nS, sh = n.value, (n.value, self.T)
@@ -937,11 +926,7 @@ class Engine:
 
     def inspect_kernel_stats(self):
         """{"insp_score" | "insp_reduce" | "insp_gather": (total_ms, launches)} since set_profiling(True)."""
-        lib = self._inspect_lib()
-        ms = np.zeros(3, dtype=np.float64)
-        cnt = np.zeros(3, dtype=np.int64)
-        _check(lib, lib.gs_read_inspect_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
-        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.INSPECT_KERNEL_NAMES)}
+        return self._kernel_stats(self._product("inspect").gs_read_inspect_kernel_stats, _abi.INSPECT_KERNEL_NAMES, 3)
 
     def _inspect_maps(self, k, edges):
         """Tick k as the reference's inspect functions get it: {observer: {peer:
@@ -973,23 +958,14 @@ class Engine:
             st["inspect"]((k + 1) * st["period_hops"], self._inspect_maps(k, edges))
 
     # ---------------------------------------------------------------- mesh health
-    def _mesh_health_lib(self):
-        if not self._has_mesh_health:
-            raise ValueError("mesh health (WithMeshHealth): product library only")
-        return self.lib
-
     def mesh_health_ticks(self):
         """Ticks taken so far (gs_mesh_health_ticks)."""
-        lib = self._mesh_health_lib()
-        n = lib.gs_mesh_health_ticks(self.h)
-        if n < 0:
-            _check(lib, int(n))
-        return int(n)
+        return self._ticks(self._product("mesh_health").gs_mesh_health_ticks)
 
     def mesh_health_row(self, k):
         """Tick k: dict(hop; members, components, largest, isolated, one_sided,
         outside, eclipsed int64 [T]; comp_hist int64 [T, 32]) (gs_read_mesh_health_row)."""
-        lib = self._mesh_health_lib()
+        lib = self._product("mesh_health")
         hop = C.c_int64()
         row = np.zeros((self.T, len(_abi.MESH_ROW_FIELDS)), dtype=np.int64)
         hist = np.zeros((self.T, _abi.GS_MESH_SIZE_BINS), dtype=np.int64)
@@ -1002,7 +978,7 @@ class Engine:
         """(tick, int32 [N, T]): the newest tick and every host's component label
         per topic, the smallest host id of its component, -1 for a non-member
         (WithMeshHealth(labels=True))."""
-        lib = self._mesh_health_lib()
+        lib = self._product("mesh_health")
         tick = C.c_int64()
         lab = np.zeros((self.N, self.T), dtype=np.int32)
         _check(lib, lib.gs_read_mesh_labels(self.h, C.byref(tick), _ptr(lab, C.c_int32)))
@@ -1012,30 +988,17 @@ class Engine:
         """{"mesh_init" | "mesh_label" | "mesh_sizes" | "mesh_row": (total_ms,
         launches)} since set_profiling(True), and "iterations" / "bytes": the
         label iterations run and the bytes moved since then (or the start)."""
-        lib = self._mesh_health_lib()
-        ms = np.zeros(len(_abi.MESH_STAT_NAMES), dtype=np.float64)
-        cnt = np.zeros(len(_abi.MESH_STAT_NAMES), dtype=np.int64)
-        _check(lib, lib.gs_read_mesh_health_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
-        out = {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.MESH_KERNEL_NAMES)}
-        return dict(out, iterations=int(cnt[4]), bytes=int(cnt[5]))
+        return self._kernel_stats(self._product("mesh_health").gs_read_mesh_health_kernel_stats,
+                                  _abi.MESH_KERNEL_NAMES, len(_abi.MESH_STAT_NAMES), ("iterations", "bytes"))
 
     # ---------------------------------------------------------------- bandwidth statistics
-    def _bandwidth_lib(self):
-        if not self._has_bandwidth:
-            raise ValueError("bandwidth statistics (WithBandwidthStats): product library only")
-        return self.lib
-
     def bandwidth_ticks(self):
         """Ticks taken so far (gs_bandwidth_ticks)."""
-        lib = self._bandwidth_lib()
-        n = lib.gs_bandwidth_ticks(self.h)
-        if n < 0:
-            _check(lib, int(n))
-        return int(n)
+        return self._ticks(self._product("bandwidth").gs_bandwidth_ticks)
 
     def bandwidth_nodes(self):
         """The sampled nodes, ascending (gs_bandwidth_nodes), int32 [nS]."""
-        lib = self._bandwidth_lib()
+        lib = self._product("bandwidth")
         n = C.c_int64()
         _check(lib, lib.gs_bandwidth_num_nodes(self.h, C.byref(n)))
         nodes = np.zeros(n.value, dtype=np.int32)
@@ -1047,7 +1010,7 @@ class Engine:
         overhead); total_rpcs; hist int64 [2, 4, len(bounds) + 1] hosts by their
         bytes (egress / ingress, class); max and argmax int64 [2, 4], argmax -1
         where max is 0) (gs_read_bandwidth_row)."""
-        lib = self._bandwidth_lib()
+        lib = self._product("bandwidth")
         nb = len(self._bw_bounds) if self._bw_bounds is not None else 0
         hop, rpcs = C.c_int64(), C.c_int64()
         total = np.zeros(4, dtype=np.int64)
@@ -1060,7 +1023,7 @@ class Engine:
     def bandwidth_sampled(self, k):
         """Tick k: (bytes int64 [nS, 2, 4], rpcs int64 [nS, 2]) of the sampled
         nodes, in bandwidth_nodes() order (gs_read_bandwidth_nodes)."""
-        lib = self._bandwidth_lib()
+        lib = self._product("bandwidth")
         n = C.c_int64()
         _check(lib, lib.gs_bandwidth_num_nodes(self.h, C.byref(n)))
         b = np.zeros((n.value, 2, 4), dtype=np.int64)
@@ -1071,30 +1034,18 @@ class Engine:
     def bandwidth_kernel_stats(self):
         """{"bw_tick" | "bw_argmax" | "bw_gather": (total_ms, launches)} since
         set_profiling(True)."""
-        lib = self._bandwidth_lib()
-        ms = np.zeros(len(_abi.BANDWIDTH_KERNEL_NAMES), dtype=np.float64)
-        cnt = np.zeros(len(_abi.BANDWIDTH_KERNEL_NAMES), dtype=np.int64)
-        _check(lib, lib.gs_read_bandwidth_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
-        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.BANDWIDTH_KERNEL_NAMES)}
+        return self._kernel_stats(self._product("bandwidth").gs_read_bandwidth_kernel_stats,
+                                  _abi.BANDWIDTH_KERNEL_NAMES, len(_abi.BANDWIDTH_KERNEL_NAMES))
 
     # ---------------------------------------------------------------- mesh reach
-    def _mesh_reach_lib(self):
-        if not self._has_mesh_reach:
-            raise ValueError("mesh reach (WithMeshReach): product library only")
-        return self.lib
-
     def mesh_reach_ticks(self):
         """Ticks taken so far (gs_mesh_reach_ticks)."""
-        lib = self._mesh_reach_lib()
-        n = lib.gs_mesh_reach_ticks(self.h)
-        if n < 0:
-            _check(lib, int(n))
-        return int(n)
+        return self._ticks(self._product("mesh_reach").gs_mesh_reach_ticks)
 
     def mesh_reach_row(self, k):
         """Tick k: dict(hop; reached, unreached, ecc int64 [K, T]; depth_hist
         int64 [K, T, 64]) over the K sources (gs_read_mesh_reach_row)."""
-        lib = self._mesh_reach_lib()
+        lib = self._product("mesh_reach")
         K = max(self._reach_sources, 1)
         hop = C.c_int64()
         row = np.zeros((K, self.T, len(_abi.REACH_ROW_FIELDS)), dtype=np.int64)
@@ -1108,7 +1059,7 @@ class Engine:
         """(tick, uint8 [K, N, T]): the newest tick and every host's eager-push
         depth from every source per topic: 0 in the source's own row, 255 where
         it is not reached, depths past 254 read 254 (WithMeshReach(depths=True))."""
-        lib = self._mesh_reach_lib()
+        lib = self._product("mesh_reach")
         tick = C.c_int64()
         dep = np.zeros((max(self._reach_sources, 1), self.N, self.T), dtype=np.uint8)
         _check(lib, lib.gs_read_mesh_reach_depths(self.h, C.byref(tick), _ptr(dep, C.c_uint8)))
@@ -1119,12 +1070,8 @@ class Engine:
         (total_ms, launches)} since set_profiling(True), and "passes" / "levels"
         / "bytes": the passes and levels run and the bytes moved since then (or
         the start)."""
-        lib = self._mesh_reach_lib()
-        ms = np.zeros(len(_abi.REACH_STAT_NAMES), dtype=np.float64)
-        cnt = np.zeros(len(_abi.REACH_STAT_NAMES), dtype=np.int64)
-        _check(lib, lib.gs_read_mesh_reach_kernel_stats(self.h, _ptr(ms, C.c_double), _ptr(cnt, C.c_int64)))
-        out = {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(_abi.REACH_KERNEL_NAMES)}
-        return dict(out, passes=int(cnt[4]), levels=int(cnt[5]), bytes=int(cnt[6]))
+        return self._kernel_stats(self._product("mesh_reach").gs_read_mesh_reach_kernel_stats,
+                                  _abi.REACH_KERNEL_NAMES, len(_abi.REACH_STAT_NAMES), ("passes", "levels", "bytes"))
 
     def deliveries(self, msg_id):
         hop = np.empty(self.N, dtype=np.int32)
